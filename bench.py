@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json metric on MI355X: trace-LDE + Merkle-commit of a 2^20 x 8 f64 trace at blowup 8.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode proofs|packed] [--config cfg2|cfg3|cfg5|dowork]
-                    [--ranks processes|threads]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode proofs|packed] [--ranks processes|threads]
+                    [--dump-outputs DIR] [--full [--config cfg2|cfg3|cfg5|dowork] [--per-launch]]
 
 A "step" is one pass of the hot path (Prover::build_trace_commitment, /root/reference/prover/src/lib.rs:615-670)
 over one synthetic trace that is already resident in HBM: interpolate 8 columns -> evaluate over the 8 cosets into
@@ -24,17 +24,30 @@ WF_BENCH_BACKEND=gloo (processes) / loopback (threads) rehearses the multi-rank 
 than ranks: the ranks share the device and the bytes of the collectives travel over a torch.distributed gloo group /
 through host memory (wf_transport).
 
---config (single GPU) prints the same line for the other workloads of the record: cfg3 (2^22 x 64 f64), cfg5 (f128 2^18 x 10),
-dowork (the reference's example at its defaults: 512 packed f128 traces of 2^10); the headline stays cfg2.
+A plain run sets up, warms up, times the K steps, writes the outputs of the last step if --dump-outputs is given and
+prints the line; everything else the record holds is measured only under --full.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
-  alu            : the step against the time its butterflies and BLAKE3 compressions take at the rates the same instruction
-                   sequences reach in isolation -- measured IN THIS RUN (csrc/yardstick.hip), with the clocks both ran at
+--full (off by default) adds the measurements that take runs of their own: the `alu` yardstick, `with_transfers`,
+`cpu_baseline` (with its root-parity gate against the CPU oracle); and it admits the record's other workloads and
+finer passes:
+  --config (single GPU) prints the same line for the other workloads of the record: cfg3 (2^22 x 64 f64), cfg5 (f128
+      2^18 x 10), dowork (the reference's example at its defaults: 512 packed f128 traces of 2^10); the headline stays cfg2.
+  --per-launch: a separate pass after the timed region with an event per kernel launch.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last step computed -- the arrays the caller of
+wf_trace_commit_dev receives -- as DIR/<name>.npy: root (32 bytes), and a fixed, seeded sample of rows of nodes and
+leaves (bytes as float32), of lde and polys (each u64 word as two exact 32-bit limbs, low first, in float64); at most
+12 MiB per array.  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) with these extra objects:
   roofline       : dominant logical kernel, its algorithmic bytes per launch
                    / its HIP-event duration measured inside the timed region, against the 8 TB/s HBM peak
-  cpu_baseline   : the CPU oracle (oracle/, "port" of the reference's concurrent path) timed on this box's host
-                   cores on full commitments of the same workload (rank 0, N == 1 only)
-  with_transfers : the same commitment through the host-buffer and the resident entry points (PCIe included;
+  alu            : (--full) the step against the time its butterflies and BLAKE3 compressions take at the rates the same
+                   instruction sequences reach in isolation -- measured IN THIS RUN (csrc/yardstick.hip), with the clocks
+                   both ran at
+  cpu_baseline   : (--full) the CPU oracle (oracle/, "port" of the reference's concurrent path) timed on the host cores
+                   on full commitments of the same workload (rank 0, N == 1 only)
+  with_transfers : (--full) the same commitment through the host-buffer and the resident entry points (PCIe included;
                    N == 1 only, outside the timed region; never `value`)
 """
 import argparse
@@ -506,6 +519,36 @@ def with_transfers(ctx, capi, params, trace_host, gpu_root):
     return out
 
 
+DUMP_SEED = 0x44554D50          # the rows sampled by --dump-outputs: fixed, so that two builds dump the same positions
+DUMP_MAX_ROWS = 1 << 16
+DUMP_MAX_BYTES = 12 << 20       # per array, as written (4 arrays + the root stay under 64 MB)
+
+
+def dump_outputs(torch, out_dir, root, arrays):
+    """--dump-outputs: write the outputs of the last timed step as out_dir/<name>.npy.  root: uint8 (32,) tensor, written
+    whole.  arrays: name -> (tensor, row_elems) -- the tensor is viewed as rows of row_elems elements and a seeded sample
+    of at most DUMP_MAX_ROWS rows (all of them when fewer) is written.  uint8 -> float32 bytes; int64 (u64 words) ->
+    float64 pairs of 32-bit limbs (lo, hi), both exact.  The caller has synchronised the device."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "root.npy"), root.cpu().numpy().astype(np.float32))
+    for i, (name, (t, row_elems)) in enumerate(sorted(arrays.items())):
+        rows = t.reshape(-1, row_elems)
+        limbs = t.dtype == torch.int64
+        row_bytes = row_elems * (16 if limbs else 4)
+        k = min(rows.shape[0], DUMP_MAX_ROWS, max(1, DUMP_MAX_BYTES // row_bytes))
+        if k < rows.shape[0]:
+            idx = np.sort(np.random.default_rng([DUMP_SEED, i]).choice(rows.shape[0], k, replace=False))
+            rows = rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+        a = rows.cpu().numpy()
+        if limbs:
+            a = a.view(np.uint64)
+            a = np.stack([a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)], axis=-1).astype(np.float64)
+        else:
+            a = a.astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 class TorchRcclComm:
     """Fallback collective for --mode proofs when wf_comm could not be created: torch.distributed over RCCL."""
     transport = "torch"
@@ -779,14 +822,22 @@ def main():
     ap.add_argument("--config", choices=tuple(CONFIGS), default="cfg2",
                     help="workload (single GPU for all but cfg2): cfg2 = the metric; cfg3 = 2^22 x 64 f64; cfg5 = f128 2^18 x 10; "
                          "dowork = the reference's example defaults (512 packed f128 traces of 2^10)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-transfers", action="store_true")
-    ap.add_argument("--per-launch", action="store_true", help="also report HIP-event times of every kernel launch")
+    ap.add_argument("--full", action="store_true",
+                    help="the whole record: in-run ALU yardstick, transfers, CPU baseline; admits --config and --per-launch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave the CPU baseline out")
+    ap.add_argument("--no-transfers", action="store_true", help="(--full) leave with_transfers out")
+    ap.add_argument("--per-launch", action="store_true", help="(--full) also report HIP-event times of every kernel launch")
     ap.add_argument("--inject-fault", choices=("root", "hang"), default=None,
                     help="test hook (tests/test_gpu_multi_device.py), applied AFTER the timed region: 'root' flips a byte of a "
                          "root on rank 1 so that the parity gate must fire; 'hang' makes rank 1 sleep so that the launcher's limit must")
     args = ap.parse_args()
 
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.config != "cfg2" or args.per_launch):
+        sys.exit("--config other than cfg2 and --per-launch belong to the full record: add --full")
     if args.config != "cfg2" and (args.gpus > 1 or args.mode != "proofs"):
         sys.exit("--config other than cfg2 is a single-GPU record of the default mode (the multi-GPU modes run the metric's workload)")
     # N > 1 as a plain command: the route is chosen HERE, before this process has touched the GPU -- child processes (never
@@ -872,9 +923,10 @@ def rank_main(args, rank, world, local_rank, route, shared):
 
     stream = torch.cuda.Stream(device=device)
     torch.cuda.synchronize()
-    clock_files = gpu_clock_files(torch, dev_index) if rank == 0 else []
-    # the yardstick of the `alu` object: measured in THIS run on THIS GPU, before the timed region
-    yard = yardstick(torch, dev_index, clock_files, CONFIGS[args.config]['field'] == 'f64') if rank == 0 else None
+    # --full: the driver's clock reading and the yardstick of the `alu` object, measured in THIS run on THIS GPU, before
+    # the timed region
+    clock_files = gpu_clock_files(torch, dev_index) if rank == 0 and args.full else []
+    yard = yardstick(torch, dev_index, clock_files, CONFIGS[args.config]['field'] == 'f64') if rank == 0 and args.full else None
     ctx.profile_enable(1)  # HIP events at the logical-kernel boundaries of every timed step (5 per step, ~1 %)
     per_launch = {}
 
@@ -927,6 +979,13 @@ def rank_main(args, rank, world, local_rank, route, shared):
         # HIP events recorded on the launch stream in front of every kernel of the K timed steps
         for name, ms in ctx.profile_read():
             per_launch.setdefault(name, []).append(ms)
+
+    if args.dump_outputs and rank == 0:
+        # the buffers still hold the last timed step's results (nothing above writes them); the gates below reuse them
+        outs = {"polys": (polys, words), "lde": (lde, row_width * words), "leaves": (leaves, 32), "nodes": (nodes, 32)}
+        if packed and comm is not None:
+            outs["top"] = (top, 32)
+        dump_outputs(torch, args.dump_outputs, roots[args.steps - 1], outs)
 
     per_rank_ms, comm_info = None, None
     if comm is not None:
@@ -1023,8 +1082,10 @@ def rank_main(args, rank, world, local_rank, route, shared):
                                                      "timed_steps": sampler.summary(),
                                                      "source": "hwmon freq1_input (sclk) of this GPU, read in a loop by a host thread"},
                         "ideal_ms": ideal, "frac": ideal / ms_per_step})
+        elif yard is None:
+            alu["not_measured"] = "the in-run yardstick is part of the full record (--full)"
         else:
-            alu["error"] = (yard or {}).get("error", "not measured")
+            alu["error"] = yard.get("error", "not measured")
         out = {
             "metric": ("trace-LDE + Merkle-commit field-ops/s (wall-clock ms in ms_per_step), 2^20x8 f64 trace blowup=8" if args.config == "cfg2"
                        else f"trace-LDE + Merkle-commit field-ops/s (wall-clock ms in ms_per_step), {args.config} (not the headline metric)"),
@@ -1073,7 +1134,7 @@ def rank_main(args, rank, world, local_rank, route, shared):
             "root": root_hex,
             "roots_gathered": n_roots,
         }
-        if world == 1 and not packed:
+        if world == 1 and not packed and args.full:
             th = trace.cpu().numpy().view("uint64")
             th = th.reshape(n_traces, n_cols, R) if is64 else th.reshape(n_traces, n_cols, R, 2)
             # the two side measurements must not cost the line its timed result: a failure in them is reported in place

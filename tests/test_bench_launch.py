@@ -63,6 +63,45 @@ def test_cpu_budget_reads_the_cgroup_quota(tmp_path, monkeypatch):
     assert det["quota_cpus"] == 3.0 and usable == min(3, det["affinity"])
 
 
+def test_plain_run_refuses_what_belongs_to_the_full_record():
+    """--config other than cfg2 and --per-launch need --full; --steps must be at least 1 (refused before any GPU work)."""
+    for args in (("--config", "cfg5"), ("--per-launch",), ("--steps", "0")):
+        out = run_bench(*args, "--warmup", "0", timeout=120)
+        assert out.returncode != 0, args
+        assert "--full" in out.stderr or "--steps" in out.stderr, out.stderr[-2000:]
+        assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_writes_exact_seeded_samples(tmp_path):
+    """bench.dump_outputs on host tensors: the root whole, a fixed sample of rows of the larger arrays, u64 words as exact
+    32-bit limbs (float64), bytes as float32, under 64 MB in all; the same sample on every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(3)
+    lde = torch.randint(-2**63, 2**63 - 1, ((1 << 21) * 8,), dtype=torch.int64, generator=g)
+    polys = torch.randint(-2**63, 2**63 - 1, ((1 << 18) * 8,), dtype=torch.int64, generator=g)
+    nodes = torch.randint(0, 256, (1 << 21, 32), dtype=torch.uint8, generator=g)
+    small = torch.randint(0, 256, (100, 32), dtype=torch.uint8, generator=g)
+    arrays = {"lde": (lde, 8), "polys": (polys, 1), "nodes": (nodes, 32), "leaves": (small, 32)}
+    bench.dump_outputs(torch, str(tmp_path / "a"), nodes[1], arrays)
+    bench.dump_outputs(torch, str(tmp_path / "b"), nodes[1], arrays)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["lde.npy", "leaves.npy", "nodes.npy", "polys.npy", "root.npy"]
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert np.array_equal(got[n[:-4]], np.load(tmp_path / "b" / n)), n
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    assert got["root"].dtype == np.float32 and np.array_equal(got["root"].astype(np.uint8), nodes[1].numpy())
+    assert np.array_equal(got["leaves"].astype(np.uint8), small.numpy())      # fewer rows than the sample: all of them
+    assert got["lde"].dtype == np.float64 and got["lde"].shape == (bench.DUMP_MAX_ROWS, 8, 2)
+    words = got["lde"][..., 0].astype(np.uint64) | (got["lde"][..., 1].astype(np.uint64) << np.uint64(32))
+    rows = {bytes(r) for r in lde.numpy().view(np.uint64).reshape(-1, 8)}
+    assert all(bytes(r) in rows for r in words)                               # exact rows of the LDE
+    assert len({bytes(r) for r in got["nodes"].astype(np.uint8)}) == bench.DUMP_MAX_ROWS
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["proofs", "packed"])
 def test_two_ranks_on_one_device_gloo_rehearsal(capi, mode):
