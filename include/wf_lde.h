@@ -1,7 +1,8 @@
 /*
  * wf_lde.h -- C ABI of libwf_lde.so: MI355X (gfx950) implementation of the winter-prover hot path
  *   trace / constraint low-degree extension (radix-2 NTT over the f64 and f128 base fields, coset evaluation)
- *   + BLAKE3-256 Merkle commitment of the extended rows, including STARKPack's combined-row commitment.
+ *   + BLAKE3-256 Merkle commitment of the extended rows, including STARKPack's combined-row commitment
+ *   (or Sha3_256, the reference's other byte-digest hasher: enum wf_hasher).
  *
  * The reference (Rust) has no FFI layer; the seam these entry points replace is the pair of provided methods
  *   Prover::build_trace_commitment       /root/reference/prover/src/lib.rs:615-670
@@ -36,6 +37,10 @@ extern "C" {
 typedef struct wf_ctx wf_ctx;
 
 enum wf_field { WF_FIELD_F64 = 1, WF_FIELD_F128 = 2 };
+/* The reference's `H: ElementHasher` type parameter (Prover::HashFn): BLAKE3 (crypto/src/hash/blake/mod.rs; Blake3_256 or
+ * Blake3_192 by digest_bytes) or Sha3_256 (crypto/src/hash/sha/mod.rs:17-57; 32-byte digests only).  With Sha3_256 a leaf is
+ * SHA3-256 of the row's canonical bytes and nodes[i] = SHA3-256(nodes[2i] || nodes[2i+1]); every layout is unchanged. */
+enum wf_hasher { WF_HASH_BLAKE3 = 0, WF_HASH_SHA3_256 = 1 };
 
 enum wf_status {
     WF_OK = 0,
@@ -51,7 +56,8 @@ enum wf_status {
     WF_ERR_ARG = -19,          /* null pointer or other malformed argument */
     WF_ERR_BUSY = -20,         /* the context is inside a call of another thread (one call at a time per wf_ctx) */
     WF_ERR_HIP = -30,          /* HIP runtime failure (no device, out of memory, launch failure) */
-    WF_ERR_DIGEST = -31,       /* digest_bytes is neither 32 (Blake3_256) nor 24 (Blake3_192) */
+    WF_ERR_DIGEST = -31,       /* digest_bytes is neither 32 (Blake3_256) nor 24 (Blake3_192); unknown hasher id; Sha3_256
+                                * with digest_bytes other than 32 (wf_params, or the context's pair of setters) */
     WF_ERR_COMM = -32          /* RCCL (or caller-supplied transport) failure, librccl.so.1 not loadable */
 };
 
@@ -70,7 +76,7 @@ typedef struct wf_params {
                               * reference's Vec<ByteDigest<N>>; DEVICE arrays (d_leaves, d_nodes of the *_dev forms, resident
                               * handles) are always 32-byte slots with the digest in front and zeros behind; root_out[32]
                               * is the digest zero-padded (Digest::as_bytes, crypto/src/hash/mod.rs:107-113) */
-    uint32_t reserved;       /* must be 0 */
+    uint32_t hasher;         /* enum wf_hasher; 0 = BLAKE3 (the field was `reserved, must be 0`: same offset and size) */
     uint8_t domain_offset[16]; /* StarkDomain::offset() as a canonical little-endian integer (7 for f64, 3 for f128) */
 } wf_params;
 
@@ -96,6 +102,11 @@ int wf_ctx_release_cached(wf_ctx *ctx);
  * functions (the reference's `H: ElementHasher` type parameter, one per Prover): 32 = Blake3_256 (default), 24 =
  * Blake3_192.  Layout rules as for wf_params::digest_bytes. */
 int wf_ctx_set_digest_bytes(wf_ctx *ctx, uint32_t digest_bytes);
+/* The other half of that hasher: WF_HASH_BLAKE3 (default) or WF_HASH_SHA3_256, for the same entry points (wf_hash_rows,
+ * wf_merkle_build, wf_merkle_build_dev, wf_fri_layer_commit*, the layers and the remainder digest of a wf_fri_prover).
+ * The pair must stay consistent: Sha3_256 on a 24-byte context, or 24 bytes on a Sha3_256 context, is refused with
+ * WF_ERR_DIGEST and changes nothing (go through BLAKE3 / 32 bytes).  Commitments carry theirs in wf_params::hasher. */
+int wf_ctx_set_hasher(wf_ctx *ctx, uint32_t hasher);
 /* Diagnostic (needs no device): the digit passes the commitment path uses for a transform of 2^log2_n rows over
  * n_segments segments (a segment = 8 f64 / 4 f128 base columns); returns the number of passes (<= 4), digits_out[i] =
  * log2 of the tile rows of pass i (the last one is the pass that writes the row-major LDE), or a negative status. */
@@ -173,7 +184,9 @@ int wf_constraint_commit_dev(wf_ctx *ctx, const wf_params *p, const void *d_poly
  *   d_leaves_shard : R * coset_count digests in the same local order (each leaf needs only its own row of every trace)
  * d_polys may be NULL.  The ranks then all-gather the leaf shards (the path's one exchange, RCCL), interleave them
  * to natural order (wf_comm_all_gather_leaf_shards) and build the tree with wf_merkle_build_dev -- or use
- * wf_trace_commit_sharded_dev, which also shards the interpolation and the tree. */
+ * wf_trace_commit_sharded_dev, which also shards the interpolation and the tree.
+ * The multi-GPU forms (this one, wf_trace_commit_sharded_dev, wf_trace_commit_sharded_resident) are BLAKE3 only: any other
+ * p->hasher is refused with WF_ERR_ARG before anything is launched or exchanged. */
 int wf_trace_commit_shard_dev(wf_ctx *ctx, const wf_params *p, uint32_t coset_begin, uint32_t coset_count,
                               const void *d_trace, void *d_polys, void *d_lde_shard, void *d_leaves_shard,
                               void *stream);
@@ -541,8 +554,8 @@ int wf_fft_interpolate_poly_with_offset(wf_ctx *ctx, uint32_t field, uint32_t ex
                                         const uint8_t domain_offset[16]);
 /* RowMatrix::evaluate_polys_over::<8> alone (row_matrix.rs:82-98): polys -> one row-major matrix. */
 int wf_evaluate_polys_over(wf_ctx *ctx, const wf_params *p, const void *const *poly_cols, void *lde_out);
-/* ElementHasher::hash_elements for Blake3_256 (crypto/src/hash/blake/mod.rs:46-59) applied to n_rows rows of
- * row_elems base elements each (rows contiguous): digests_out gets n_rows*32 bytes. */
+/* ElementHasher::hash_elements of the context's hasher (Blake3_256 by default: crypto/src/hash/blake/mod.rs:46-59) applied
+ * to n_rows rows of row_elems base elements each (rows contiguous): digests_out gets n_rows digests. */
 int wf_hash_rows(wf_ctx *ctx, uint32_t field, const void *rows, size_t n_rows, size_t row_elems, uint8_t *digests_out);
 /* MerkleTree::new (crypto/src/merkle/mod.rs:117-136): leaves -> nodes (both n_leaves*32 bytes). */
 int wf_merkle_build(wf_ctx *ctx, const uint8_t *leaves, size_t n_leaves, uint8_t *nodes_out);

@@ -240,10 +240,30 @@ inline unsigned ilog2_exact(size_t v, const char *what) {
     return l;
 }
 
+// The reference's `H: ElementHasher` type parameter (Prover::HashFn) as a tag: Prover(device, Sha3_256::ID).  The context's
+// entry points without wf_params (FRI, wf_hash_rows, wf_merkle_build) and every commitment built through the prover use it.
+struct Blake3_256 {
+    static constexpr uint32_t ID = WF_HASH_BLAKE3;
+};
+struct Sha3_256 {
+    static constexpr uint32_t ID = WF_HASH_SHA3_256;
+};
+
 class Prover {
   public:
-    explicit Prover(int device = 0) { wf_check(wf_ctx_create(device, &ctx_)); }
+    explicit Prover(int device = 0, uint32_t hasher = Blake3_256::ID) : hasher_(hasher) {
+        wf_check(wf_ctx_create(device, &ctx_));
+        if (hasher != Blake3_256::ID) {
+            const int rc = wf_ctx_set_hasher(ctx_, hasher);
+            if (rc) {
+                wf_ctx_destroy(ctx_);
+                ctx_ = nullptr;
+                wf_check(rc);
+            }
+        }
+    }
     ~Prover() { wf_ctx_destroy(ctx_); }
+    uint32_t hasher() const { return hasher_; }
     Prover(const Prover &) = delete;
     Prover &operator=(const Prover &) = delete;
     wf_ctx *context() const { return ctx_; }
@@ -297,7 +317,7 @@ class Prover {
 
   private:
     template <class E>
-    static wf_params params(size_t rows, size_t cols, size_t n_traces, const StarkDomain &domain) {
+    wf_params params(size_t rows, size_t cols, size_t n_traces, const StarkDomain &domain) const {
         if (rows != domain.trace_length()) throw std::invalid_argument("matrix length does not match the domain");
         wf_params p;
         std::memset(&p, 0, sizeof(p));
@@ -308,11 +328,13 @@ class Prover {
         p.n_cols = (uint32_t)cols;
         p.n_traces = (uint32_t)n_traces;
         p.digest_bytes = 32;
+        p.hasher = hasher_;
         unsigned __int128 off = domain.offset();
         std::memcpy(p.domain_offset, &off, 16);
         return p;
     }
     wf_ctx *ctx_ = nullptr;
+    uint32_t hasher_ = Blake3_256::ID;
 };
 
 // ------------------------------------------------------------------------------------------------- resident commitments
@@ -394,6 +416,7 @@ inline std::pair<std::unique_ptr<TraceCommitment<E>>, std::vector<ColMatrix<E>>>
     p.n_cols = (uint32_t)cols;
     p.n_traces = (uint32_t)traces.size();
     p.digest_bytes = 32;
+    p.hasher = prover.hasher();
     unsigned __int128 off = domain.offset();
     std::memcpy(p.domain_offset, &off, 16);
     std::vector<const void *> in;
@@ -426,6 +449,7 @@ inline std::unique_ptr<TraceCommitment<E>> build_resident_constraint_commitment(
     p.n_cols = (uint32_t)cols;
     p.n_traces = 1;
     p.digest_bytes = 32;
+    p.hasher = prover.hasher();
     unsigned __int128 off = domain.offset();
     std::memcpy(p.domain_offset, &off, 16);
     std::vector<const void *> in;
@@ -452,6 +476,7 @@ inline std::unique_ptr<TraceCommitment<E>> build_resident_constraint_commitment_
     p.n_cols = (uint32_t)num_cols;
     p.n_traces = 1;
     p.digest_bytes = 32;
+    p.hasher = prover.hasher();
     unsigned __int128 off = domain.offset();
     std::memcpy(p.domain_offset, &off, 16);
     std::vector<const void *> in;

@@ -19,7 +19,8 @@ pub struct WfParams {
     pub n_cols: u32,
     pub n_traces: u32,
     pub digest_bytes: u32,
-    pub reserved: u32,
+    /// `enum wf_hasher`: 0 = BLAKE3, 1 = Sha3_256 (32-byte digests only)
+    pub hasher: u32,
     pub domain_offset: [u8; 16],
 }
 
@@ -156,6 +157,8 @@ extern "C" {
         comm: *mut WfComm, d_roots: *const c_void, n_roots: usize, d_all: *mut c_void, stream: *mut c_void,
     ) -> c_int;
     pub fn wf_ctx_set_digest_bytes(ctx: *mut WfCtx, digest_bytes: u32) -> c_int;
+    /// The other half of the context's hasher (FRI, `wf_hash_rows`, `wf_merkle_build`): 0 = BLAKE3, 1 = Sha3_256.
+    pub fn wf_ctx_set_hasher(ctx: *mut WfCtx, hasher: u32) -> c_int;
     /// A stream of proofs: returns once the columns are on their way; `wf_commitment_wait` (or `wf_commitment_root`) completes it.
     pub fn wf_trace_commit_resident_async(
         ctx: *mut WfCtx, p: *const WfParams, trace_cols: *const *const c_void, out: *mut *mut WfCommitment,

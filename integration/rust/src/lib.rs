@@ -59,15 +59,23 @@ impl WfField for f128::BaseElement {
 
 /// Hashers the library implements: the digest is a byte array of `DIGEST_BYTES` bytes, written by the library as such
 /// (`ByteDigest<N>`, `crypto/src/hash/mod.rs:84-85`): `Blake3_256` (32) and `Blake3_192` (24: the BLAKE3 output truncated,
-/// 48-byte merges, `crypto/src/hash/blake/mod.rs:68-114`).  Host arrays of digests hold `DIGEST_BYTES` per entry.
+/// 48-byte merges, `crypto/src/hash/blake/mod.rs:68-114`) and `Sha3_256` (32, `crypto/src/hash/sha/mod.rs:17-57`).  Host
+/// arrays of digests hold `DIGEST_BYTES` per entry; `HASHER` is the `enum wf_hasher` id that goes into `wf_params::hasher`.
 pub trait WfHasher: ElementHasher + Hasher {
     const DIGEST_BYTES: u32;
+    const HASHER: u32;
 }
 impl<B: StarkField> WfHasher for crypto::hashers::Blake3_256<B> {
     const DIGEST_BYTES: u32 = 32;
+    const HASHER: u32 = 0;
 }
 impl<B: StarkField> WfHasher for crypto::hashers::Blake3_192<B> {
     const DIGEST_BYTES: u32 = 24;
+    const HASHER: u32 = 0;
+}
+impl<B: StarkField> WfHasher for crypto::hashers::Sha3_256<B> {
+    const DIGEST_BYTES: u32 = 32;
+    const HASHER: u32 = 1;
 }
 
 // CONTEXT
@@ -89,6 +97,16 @@ impl WfContext {
     pub fn as_ptr(&self) -> *mut WfCtx {
         self.raw
     }
+    /// The hasher of the entry points that take no `wf_params` (the FRI prover, `wf_hash_rows`, `wf_merkle_build`).
+    pub fn set_hasher<H: WfHasher>(&self) -> Result<(), String> {
+        if H::HASHER == 0 {
+            check(unsafe { wf_ctx_set_hasher(self.raw, 0) })?;
+            check(unsafe { wf_ctx_set_digest_bytes(self.raw, H::DIGEST_BYTES) })
+        } else {
+            check(unsafe { wf_ctx_set_digest_bytes(self.raw, H::DIGEST_BYTES) })?;
+            check(unsafe { wf_ctx_set_hasher(self.raw, H::HASHER) })
+        }
+    }
 }
 impl Drop for WfContext {
     fn drop(&mut self) {
@@ -105,7 +123,7 @@ fn check(rc: i32) -> Result<(), String> {
 }
 
 fn params<B: WfField, E: FieldElement<BaseField = B>>(
-    trace_len: usize, n_cols: usize, n_traces: usize, domain: &StarkDomain<B>, digest_bytes: u32,
+    trace_len: usize, n_cols: usize, n_traces: usize, domain: &StarkDomain<B>, digest_bytes: u32, hasher: u32,
 ) -> WfParams {
     let mut p = WfParams {
         field: B::WF_FIELD,
@@ -115,7 +133,7 @@ fn params<B: WfField, E: FieldElement<BaseField = B>>(
         n_cols: n_cols as u32,
         n_traces: n_traces as u32,
         digest_bytes,
-        reserved: 0,
+        hasher,
         domain_offset: [0; 16],
     };
     // Serializable for a base element writes its canonical little-endian integer (f64/mod.rs:605-610, f128 likewise)
@@ -140,7 +158,7 @@ where
     assert!(!traces.is_empty(), "at least one trace is required");
     let (r, c, n) = (traces[0].num_rows(), traces[0].num_cols(), traces.len());
     assert!(traces.iter().all(|t| t.num_rows() == r && t.num_cols() == c), "packed traces must have one shape");
-    let p = params::<B, E>(r, c, n, domain, H::DIGEST_BYTES);
+    let p = params::<B, E>(r, c, n, domain, H::DIGEST_BYTES, H::HASHER);
     let row_width = unsafe { wf_row_width(&p) };
     let lde_rows = r * domain.trace_to_lde_blowup();
 
@@ -189,7 +207,7 @@ where
 {
     let data = composition_poly.data(); // ColMatrix<E>: num_cols columns of trace_length coefficients
     let (r, c) = (data.num_rows(), data.num_cols());
-    let p = params::<B, E>(r, c, 1, domain, H::DIGEST_BYTES);
+    let p = params::<B, E>(r, c, 1, domain, H::DIGEST_BYTES, H::HASHER);
     let row_width = unsafe { wf_row_width(&p) };
     let lde_rows = r * domain.trace_to_lde_blowup();
 
@@ -236,7 +254,7 @@ where
         ctx: &'a WfContext, traces: &[&ColMatrix<E>], domain: &StarkDomain<B>, want_polys: bool,
     ) -> (Self, Vec<ColMatrix<E>>) {
         let (r, c, n) = (traces[0].num_rows(), traces[0].num_cols(), traces.len());
-        let p = params::<B, E>(r, c, n, domain, H::DIGEST_BYTES);
+        let p = params::<B, E>(r, c, n, domain, H::DIGEST_BYTES, H::HASHER);
         let col_ptrs: Vec<*const c_void> = traces
             .iter()
             .flat_map(|t| (0..c).map(move |i| t.get_column(i).as_ptr() as *const c_void))
@@ -265,7 +283,7 @@ where
     /// staged them when this returns, so `traces` may be dropped at once.
     pub fn commit_traces_async(ctx: &'a WfContext, traces: &[&ColMatrix<E>], domain: &StarkDomain<B>) -> Self {
         let (r, c, n) = (traces[0].num_rows(), traces[0].num_cols(), traces.len());
-        let p = params::<B, E>(r, c, n, domain, H::DIGEST_BYTES);
+        let p = params::<B, E>(r, c, n, domain, H::DIGEST_BYTES, H::HASHER);
         let col_ptrs: Vec<*const c_void> = traces
             .iter()
             .flat_map(|t| (0..c).map(move |i| t.get_column(i).as_ptr() as *const c_void))
@@ -285,7 +303,7 @@ where
     pub fn commit_composition_poly(ctx: &'a WfContext, poly: &CompositionPoly<E>, domain: &StarkDomain<B>) -> Self {
         let data = poly.data();
         let (r, c) = (data.num_rows(), data.num_cols());
-        let p = params::<B, E>(r, c, 1, domain, H::DIGEST_BYTES);
+        let p = params::<B, E>(r, c, 1, domain, H::DIGEST_BYTES, H::HASHER);
         let col_ptrs: Vec<*const c_void> = (0..c).map(|i| data.get_column(i).as_ptr() as *const c_void).collect();
         let mut raw = core::ptr::null_mut();
         check(unsafe { wf_constraint_commit_resident(ctx.raw, &p, col_ptrs.as_ptr(), &mut raw) })
@@ -364,7 +382,7 @@ where
         domain: &StarkDomain<B>,
     ) -> Self {
         let ce = tables[0][0].0.len();
-        let p = params::<B, E>(trace_length, num_cols, 1, domain, H::DIGEST_BYTES);
+        let p = params::<B, E>(trace_length, num_cols, 1, domain, H::DIGEST_BYTES, H::HASHER);
         let mut col_ptrs: Vec<Vec<*const c_void>> = Vec::new();
         let mut divisors: Vec<Vec<WfDivisor>> = Vec::new();
         for t in tables {

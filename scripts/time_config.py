@@ -1,11 +1,13 @@
 """Times the device-buffer form of the trace commitment for an arbitrary configuration (bring-up / tuning aid).
-    python scripts/time_config.py <field 1|2> <ext> <log2 R> <log2 blowup> <n_cols> <n_traces>"""
+    python scripts/time_config.py <field 1|2> <ext> <log2 R> <log2 blowup> <n_cols> <n_traces> [hasher 0|1]
+(hasher: 0 = BLAKE3, 1 = Sha3_256)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import starkpack_winterfell_amd.capi as capi
 
 field, ext, logR, logB, n_cols, n_traces = (int(x) for x in sys.argv[1:7])
+hasher = int(sys.argv[7]) if len(sys.argv) > 7 else capi.BLAKE3
 dev = torch.device("cuda", 0)
 ctx = capi.Context(0)
 w = 1 if field == 1 else 2
@@ -17,7 +19,7 @@ rw = 8 * ((n_cols * ext + 7) // 8)
 lde = torch.empty(n_traces * N * rw * w, dtype=torch.int64, device=dev)
 leaves = torch.empty((N, 32), dtype=torch.uint8, device=dev)
 nodes = torch.empty((N, 32), dtype=torch.uint8, device=dev)
-p = capi.make_params(field, ext, logR, logB, n_cols, n_traces)
+p = capi.make_params(field, ext, logR, logB, n_cols, n_traces, hasher=hasher)
 s = torch.cuda.Stream(device=dev)
 ctx.profile_enable(2)
 with torch.cuda.stream(s):
@@ -33,5 +35,5 @@ with torch.cuda.stream(s):
 acc = {}
 for k, v in ctx.profile_read():
     acc.setdefault(k, []).append(v)
-print(f"field={field} ext={ext} R=2^{logR} blowup={1<<logB} cols={n_cols} traces={n_traces}: {e0.elapsed_time(e1)/K:.3f} ms",
+print(f"field={field} ext={ext} R=2^{logR} blowup={1<<logB} cols={n_cols} traces={n_traces} hasher={hasher}: {e0.elapsed_time(e1)/K:.3f} ms",
       {k: round(sum(v)/len(v), 4) for k, v in acc.items()})

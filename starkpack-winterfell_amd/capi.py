@@ -15,11 +15,12 @@ import numpy as np
 from .build import lib_path
 
 F64, F128 = 1, 2
+BLAKE3, SHA3_256 = 0, 1  # enum wf_hasher
 ELEM_WORDS = {F64: 1, F128: 2}
 
 SYMBOLS = [
     "wf_ctx_create", "wf_ctx_destroy", "wf_last_error", "wf_device_count", "wf_ctx_synchronize", "wf_ctx_stream",
-    "wf_ctx_release_cached", "wf_ctx_set_digest_bytes", "wf_plan_digits", "wf_commitment_query", "wf_ctx_profile_enable", "wf_ctx_profile_read", "wf_params_check", "wf_elem_bytes", "wf_row_width", "wf_column_bytes", "wf_lde_bytes", "wf_digests_bytes",
+    "wf_ctx_release_cached", "wf_ctx_set_digest_bytes", "wf_ctx_set_hasher", "wf_plan_digits", "wf_commitment_query", "wf_ctx_profile_enable", "wf_ctx_profile_read", "wf_params_check", "wf_elem_bytes", "wf_row_width", "wf_column_bytes", "wf_lde_bytes", "wf_digests_bytes",
     "wf_trace_commit", "wf_constraint_commit", "wf_trace_commit_dev", "wf_constraint_commit_dev",
     "wf_trace_commit_shard_dev", "wf_merkle_build_dev", "wf_trace_commit_resident", "wf_trace_commit_resident_async", "wf_commitment_wait", "wf_constraint_commit_resident", "wf_commitment_destroy", "wf_commitment_root",
     "wf_commitment_info", "wf_commitment_read_rows", "wf_commitment_read_lde", "wf_commitment_read_lde_strided", "wf_deep_compose", "wf_commitment_evaluate_polys_at_points", "wf_constraint_commit_from_evaluations", "wf_constraint_commit_from_tables", "wf_commitment_query_many", "wf_commitment_prove", "wf_commitment_prove_batch",
@@ -47,7 +48,7 @@ class Params(C.Structure):
     _fields_ = [
         ("field", C.c_uint32), ("ext_degree", C.c_uint32), ("log2_trace_len", C.c_uint32),
         ("log2_blowup", C.c_uint32), ("n_cols", C.c_uint32), ("n_traces", C.c_uint32),
-        ("digest_bytes", C.c_uint32), ("reserved", C.c_uint32), ("domain_offset", C.c_uint8 * 16),
+        ("digest_bytes", C.c_uint32), ("hasher", C.c_uint32), ("domain_offset", C.c_uint8 * 16),
     ]
 
 
@@ -77,11 +78,12 @@ class Query(C.Structure):
                 ("node_counts", C.c_void_p), ("n_vectors", C.c_size_t), ("n_nodes", C.c_size_t), ("depth", C.c_uint32)]
 
 
-def make_params(field, ext_degree, log2_trace_len, log2_blowup, n_cols, n_traces=1, offset=None, digest_bytes=32) -> Params:
-    """digest_bytes: 32 = Blake3_256, 24 = Blake3_192 (host arrays of digests are then 24 bytes per entry)."""
+def make_params(field, ext_degree, log2_trace_len, log2_blowup, n_cols, n_traces=1, offset=None, digest_bytes=32, hasher=0) -> Params:
+    """digest_bytes: 32 = Blake3_256, 24 = Blake3_192 (host arrays of digests are then 24 bytes per entry); hasher: BLAKE3 (0)
+    or SHA3_256 (1: Sha3_256, 32-byte digests only)."""
     if offset is None:
         offset = 7 if field == F64 else 3  # ProofOptions::domain_offset = B::GENERATOR, air/src/options.rs:199-201
-    p = Params(field, ext_degree, log2_trace_len, log2_blowup, n_cols, n_traces, digest_bytes, 0)
+    p = Params(field, ext_degree, log2_trace_len, log2_blowup, n_cols, n_traces, digest_bytes, hasher)
     p.domain_offset[:] = list(int(offset).to_bytes(16, "little"))
     return p
 
@@ -198,6 +200,7 @@ def load():
         L.wf_device_count.argtypes = []
         L.wf_ctx_release_cached.argtypes = [vp]
         L.wf_ctx_set_digest_bytes.argtypes = [vp, u32]
+        L.wf_ctx_set_hasher.argtypes = [vp, u32]
         L.wf_plan_digits.argtypes = [u32, u32, u32, C.POINTER(u32)]
         L.wf_commitment_query.argtypes = [vp, vp, sz, vp, vp, vp, sz, vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(u32)]
         pu32, pu64 = C.POINTER(u32), C.POINTER(C.c_uint64)
@@ -276,7 +279,8 @@ class Context:
         self._h = C.c_void_p()
         _check(load().wf_ctx_create(device, C.byref(self._h)))
         self.device = device
-        self.digest_bytes = 32  # hasher of the entry points without wf_params (set_digest_bytes)
+        self.digest_bytes = 32  # hasher of the entry points without wf_params (set_digest_bytes, set_hasher)
+        self.hasher = BLAKE3
         # Handles created on this context (commitments, FRI provers, communicators): the C ABI wants them destroyed
         # before it.  References from the children keep the context alive in normal operation, but the interpreter's
         # final garbage collection runs the finalisers of a dead cycle in no particular order -- so close() takes the
@@ -292,6 +296,12 @@ class Context:
         """wf_ctx_set_digest_bytes: 32 = Blake3_256 (default), 24 = Blake3_192 for hash_rows / merkle_build / the FRI entry points."""
         _check(load().wf_ctx_set_digest_bytes(self._h, n))
         self.digest_bytes = n
+
+    def set_hasher(self, hasher: int):
+        """wf_ctx_set_hasher: BLAKE3 (default) or SHA3_256 for hash_rows / merkle_build / the FRI entry points (an inconsistent
+        pair -- Sha3_256 with 24-byte digests -- raises WfError -31 and changes nothing)."""
+        _check(load().wf_ctx_set_hasher(self._h, hasher))
+        self.hasher = hasher
 
     def release_cached(self):
         """Return the parked buffers of destroyed resident commitments to the driver (wf_ctx_release_cached)."""

@@ -295,11 +295,19 @@ int check_params(const wf_params *p, bool constraint) {
     if (p->n_traces < 1 || (constraint && p->n_traces != 1)) return fail(WF_ERR_TRACES, "invalid number of traces %u", p->n_traces);
     if (p->digest_bytes != 32 && p->digest_bytes != 24)
         return fail(WF_ERR_DIGEST, "digest_bytes must be 32 (Blake3_256) or 24 (Blake3_192), got %u", p->digest_bytes);
-    if (p->reserved != 0) return fail(WF_ERR_ARG, "reserved field must be zero");
+    if (p->hasher > WF_HASH_SHA3_256) return fail(WF_ERR_DIGEST, "unknown hasher id %u (0 = BLAKE3, 1 = Sha3_256)", p->hasher);
+    if (p->hasher == WF_HASH_SHA3_256 && p->digest_bytes != 32)
+        return fail(WF_ERR_DIGEST, "Sha3_256 has 32-byte digests, got digest_bytes %u", p->digest_bytes);
     u128 off;
     memcpy(&off, p->domain_offset, 16);
     const u128 mod = p->field == WF_FIELD_F64 ? (u128)F64::P : F128::P();
     if (off == 0 || off >= mod) return fail(WF_ERR_OFFSET, "domain offset must be a non-zero field element");
+    return 0;
+}
+
+int check_blake3_only(const wf_params *p, const char *what) {
+    if (p->hasher != WF_HASH_BLAKE3)
+        return fail(WF_ERR_ARG, "%s: the multi-GPU commitments are BLAKE3 only (hasher id %u)", what, p->hasher);
     return 0;
 }
 
@@ -437,8 +445,20 @@ int wf_ctx_set_digest_bytes(wf_ctx *ctx, uint32_t digest_bytes) {
     if (!ctx) return fail(WF_ERR_ARG, "ctx is null");
     if (digest_bytes != 32 && digest_bytes != 24)
         return fail(WF_ERR_DIGEST, "digest_bytes must be 32 (Blake3_256) or 24 (Blake3_192), got %u", digest_bytes);
+    if (digest_bytes != 32 && ctx->hasher == WF_HASH_SHA3_256)
+        return fail(WF_ERR_DIGEST, "the context hashes with Sha3_256, which has 32-byte digests (got digest_bytes %u)", digest_bytes);
     WF_ENTER(ctx, nullptr);
     ctx->digest_bytes = digest_bytes;
+    return 0;
+}
+
+int wf_ctx_set_hasher(wf_ctx *ctx, uint32_t hasher) {
+    if (!ctx) return fail(WF_ERR_ARG, "ctx is null");
+    if (hasher > WF_HASH_SHA3_256) return fail(WF_ERR_DIGEST, "unknown hasher id %u (0 = BLAKE3, 1 = Sha3_256)", hasher);
+    if (hasher == WF_HASH_SHA3_256 && ctx->digest_bytes != 32)
+        return fail(WF_ERR_DIGEST, "Sha3_256 has 32-byte digests, the context is set to %u", ctx->digest_bytes);
+    WF_ENTER(ctx, nullptr);
+    ctx->hasher = hasher;
     return 0;
 }
 

@@ -33,10 +33,10 @@ static int fri_layer_commit_dev(wf_ctx *ctx, hipStream_t st, uint32_t ext, const
                        (T *)d_transposed, rows, folding, ext);
     HIP_TRY(hipGetLastError());
     prof_mark(ctx, st, "fri.hash_values");
-    int rc = path_hash_rows(ctx, st, F::FIELD_ID == 1 ? WF_FIELD_F64 : WF_FIELD_F128, d_transposed, 0, rows, folding * ext, folding * ext, 1, d_leaves, ctx->digest_bytes);
+    int rc = path_hash_rows(ctx, st, F::FIELD_ID == 1 ? WF_FIELD_F64 : WF_FIELD_F128, d_transposed, 0, rows, folding * ext, folding * ext, 1, d_leaves, ctx->digest_bytes, ctx->hasher);
     if (rc) return rc;
     prof_mark(ctx, st, "fri.merkle");
-    rc = path_merkle(ctx, st, d_leaves, rows, d_nodes, ctx->digest_bytes);
+    rc = path_merkle(ctx, st, d_leaves, rows, d_nodes, ctx->digest_bytes, ctx->hasher);
     prof_mark(ctx, st, "between_calls");
     return rc;
 }
@@ -403,7 +403,8 @@ int wf_fri_prover_commit_layer(wf_fri_prover *pr, uint8_t root_out[32]) {
     c->p.ext_degree = pr->ext;
     c->p.n_cols = pr->folding;
     c->p.n_traces = 1;
-    c->p.digest_bytes = ctx->digest_bytes;  // the context's hasher (wf_ctx_set_digest_bytes)
+    c->p.digest_bytes = ctx->digest_bytes;  // the context's hasher (wf_ctx_set_digest_bytes, wf_ctx_set_hasher)
+    c->p.hasher = ctx->hasher;
     memcpy(c->p.domain_offset, pr->offset, 16);
     c->n_rows = rows;
     c->row_width = c->epr = c->row_elems = (uint64_t)pr->folding * pr->ext;

@@ -4,6 +4,7 @@
 #include "wf_internal.hpp"
 
 #include "kernels.hpp"
+#include "keccak_kernels.hpp"
 #include "seg_kernels.hpp"
 #include "col_kernels.hpp"
 #include "fri_kernels.hpp"
@@ -680,7 +681,7 @@ static void launch_merge_chunks(hipStream_t st, const void *cvs, uint32_t n_chun
 
 template <class F>
 static int run_hash_rows(wf_ctx *ctx, hipStream_t st, const void *lde, uint64_t trace_elems, uint64_t n_rows, uint32_t row_width,
-                         uint32_t epr, uint32_t n_traces, void *leaves, uint32_t dw = 8) {
+                         uint32_t epr, uint32_t n_traces, void *leaves, uint32_t dw = 8, uint32_t hasher = WF_HASH_BLAKE3) {
     HashArgs<F> h;
     h.lde = (const typename F::T *)lde;
     h.trace_elems = trace_elems;
@@ -692,6 +693,12 @@ static int run_hash_rows(wf_ctx *ctx, hipStream_t st, const void *lde, uint64_t 
     h.digest_words = dw;
     const uint32_t threads = 256;
     const uint64_t grid = (n_rows + threads - 1) / threads;
+    if (hasher == WF_HASH_SHA3_256) {  // one lane per row absorbs the whole row, whatever its length
+        if (grid > 0x7FFFFFFFull) return fail(WF_ERR_ARG, "too many rows for one launch");
+        hipLaunchKernelGGL(k_sha3_hash_rows<F>, dim3((uint32_t)grid), dim3(threads), 0, st, h);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     const uint64_t row_bytes = (uint64_t)n_traces * epr * F::BYTES;
     if (row_bytes <= 1024) {  // single BLAKE3 chunk: one lane per row, no subtree stack
         hipLaunchKernelGGL(k_hash_rows<F>, dim3((uint32_t)grid), dim3(threads), 0, st, h);
@@ -763,8 +770,40 @@ static int run_merkle_dw(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64
     return 0;
 }
 
+// Sha3_256 tree: one lane per parent while a level still fills the chip (>= 2^15 parents, the one-lane-per-node rule of
+// run_merkle_dw), then the LDS subtree kernel, up to 9 levels per launch.  A pure kernel sequence like the BLAKE3 tree.
+static constexpr uint32_t SHA3_LEVEL_MIN_LOG = 15;
+static int run_merkle_sha3(hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes) {
+    const uint64_t *children = (const uint64_t *)leaves;
+    uint64_t n_children = n_leaves;
+    while (n_children > 1) {
+        const uint64_t n_par = n_children >> 1;
+        const uint32_t threads = 256;
+        const uint64_t grid = (n_par + threads - 1) / threads;
+        if (grid > 0x7FFFFFFFull) return fail(WF_ERR_ARG, "too many leaves for one launch");
+        if (n_par >= ((uint64_t)1 << SHA3_LEVEL_MIN_LOG)) {
+            hipLaunchKernelGGL(k_sha3_merkle_level, dim3((uint32_t)grid), dim3(threads), 0, st, (const ulonglong2 *)children,
+                               (ulonglong2 *)nodes + n_par * 2, n_par);
+            HIP_TRY(hipGetLastError());
+            n_children = n_par;
+        } else {
+            uint32_t total_levels = 0;
+            for (uint64_t t = n_children; t > 1; t >>= 1) total_levels++;
+            const uint32_t levels = std::min<uint32_t>(9, total_levels);
+            hipLaunchKernelGGL(k_sha3_merkle_subtree, dim3((uint32_t)grid), dim3(threads), 0, st, children, (uint64_t *)nodes,
+                               n_children, levels);
+            HIP_TRY(hipGetLastError());
+            n_children >>= levels;
+        }
+        children = (const uint64_t *)nodes + n_children * 4;  // that level lives at nodes[n .. 2n)
+    }
+    return 0;
+}
+
 // dw: digest words -- 8 = Blake3_256, 6 = Blake3_192 (48-byte merge inputs; the slots' last two words are zeros)
-static int run_merkle(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes, uint32_t dw = 8) {
+static int run_merkle(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes, uint32_t dw = 8,
+                      uint32_t hasher = WF_HASH_BLAKE3) {
+    if (hasher == WF_HASH_SHA3_256) return run_merkle_sha3(st, leaves, n_leaves, nodes);
     return dw == 6 ? run_merkle_dw<6>(ctx, st, leaves, n_leaves, nodes) : run_merkle_dw<8>(ctx, st, leaves, n_leaves, nodes);
 }
 
@@ -860,7 +899,9 @@ static int evaluate_and_commit(wf_ctx *ctx, hipStream_t st, const wf_params *p, 
     d.pad_in_kernel = pad_in_kernel;
     d.pad_traces = pad_traces;
     bool hashed = false;  // leaves produced by the last evaluation pass itself (one segment, one trace)
-    d.leaves = d_leaves;
+    // a hasher other than BLAKE3 has no in-pass form: without a leaf buffer no pass fuses, tail-packs or hashes by chunks
+    // (run_seg_transform), and the rows are hashed from the LDE below -- the route WF_EXP_NO_FUSED_HASH forces for BLAKE3
+    d.leaves = p->hasher == WF_HASH_BLAKE3 ? d_leaves : nullptr;
     d.hash_epr = b.total_base_cols;  // the combined row of all traces (= base_cols for one trace)
     d.digest_words = p->digest_bytes / 4;
     d.fused = &hashed;
@@ -874,12 +915,12 @@ static int evaluate_and_commit(wf_ctx *ctx, hipStream_t st, const wf_params *p, 
     if (d_leaves) {
         if (!hashed) {
             prof_mark(ctx, st, "hash_rows");
-            rc = run_hash_rows<F>(ctx, st, d_lde, Nrows * row_width, Nrows, (uint32_t)row_width, base_cols, p->n_traces, d_leaves, p->digest_bytes / 4);
+            rc = run_hash_rows<F>(ctx, st, d_lde, Nrows * row_width, Nrows, (uint32_t)row_width, base_cols, p->n_traces, d_leaves, p->digest_bytes / 4, p->hasher);
             if (rc) return rc;
         }
         if (d_nodes) {
             prof_mark(ctx, st, "merkle");
-            rc = run_merkle(ctx, st, d_leaves, Nrows, d_nodes, p->digest_bytes / 4);
+            rc = run_merkle(ctx, st, d_leaves, Nrows, d_nodes, p->digest_bytes / 4, p->hasher);
             if (rc) return rc;
         }
     }
@@ -1107,6 +1148,7 @@ int wf_trace_commit_shard_dev(wf_ctx *ctx, const wf_params *p, uint32_t coset_be
     if (!ctx) return fail(WF_ERR_ARG, "ctx is null");
     int rc = check_params(p, false);
     if (rc) return rc;
+    if ((rc = check_blake3_only(p, "wf_trace_commit_shard_dev"))) return rc;
     if (!d_trace || !d_lde_shard || !d_leaves_shard) return fail(WF_ERR_ARG, "null device buffer");
     const uint32_t blowup = 1u << p->log2_blowup;
     if (coset_count == 0 || coset_begin >= blowup || coset_count > blowup - coset_begin)
@@ -1128,7 +1170,7 @@ int wf_merkle_build_dev(wf_ctx *ctx, const void *d_leaves, size_t n_leaves, void
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     WF_ENTER(ctx, st);
     prof_mark(ctx, st, "merkle");
-    int rc = run_merkle(ctx, st, d_leaves, n_leaves, d_nodes, ctx->digest_bytes / 4);
+    int rc = run_merkle(ctx, st, d_leaves, n_leaves, d_nodes, ctx->digest_bytes / 4, ctx->hasher);
     prof_mark(ctx, st, "between_calls");
     return rc;
 }
@@ -1347,9 +1389,9 @@ int wf_hash_rows(wf_ctx *ctx, uint32_t field, const void *rows, size_t n_rows, s
     hipStream_t st = ctx->stream;
     if (bytes) HIP_TRY(hipMemcpyAsync(ctx->io[2].p, rows, bytes, hipMemcpyHostToDevice, st));
     if (field == WF_FIELD_F64)
-        rc = run_hash_rows<F64>(ctx, st, ctx->io[2].p, 0, n_rows, (uint32_t)row_elems, (uint32_t)row_elems, 1, ctx->io[3].p, ctx->digest_bytes / 4);
+        rc = run_hash_rows<F64>(ctx, st, ctx->io[2].p, 0, n_rows, (uint32_t)row_elems, (uint32_t)row_elems, 1, ctx->io[3].p, ctx->digest_bytes / 4, ctx->hasher);
     else
-        rc = run_hash_rows<F128>(ctx, st, ctx->io[2].p, 0, n_rows, (uint32_t)row_elems, (uint32_t)row_elems, 1, ctx->io[3].p, ctx->digest_bytes / 4);
+        rc = run_hash_rows<F128>(ctx, st, ctx->io[2].p, 0, n_rows, (uint32_t)row_elems, (uint32_t)row_elems, 1, ctx->io[3].p, ctx->digest_bytes / 4, ctx->hasher);
     if (rc) return rc;
     if ((rc = path_digests_to_host(ctx, st, ctx->io[3].p, digests_out, n_rows, ctx->digest_bytes))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
@@ -1368,7 +1410,7 @@ int wf_merkle_build(wf_ctx *ctx, const uint8_t *leaves, size_t n_leaves, uint8_t
     if ((rc = ensure(ctx, ctx->io[4], n_leaves * 32))) return rc;
     hipStream_t st = ctx->stream;
     if ((rc = path_digests_from_host(ctx, st, leaves, ctx->io[3].p, n_leaves, ctx->digest_bytes))) return rc;
-    rc = run_merkle(ctx, st, ctx->io[3].p, n_leaves, ctx->io[4].p, ctx->digest_bytes / 4);
+    rc = run_merkle(ctx, st, ctx->io[3].p, n_leaves, ctx->io[4].p, ctx->digest_bytes / 4, ctx->hasher);
     if (rc) return rc;
     if ((rc = path_digests_to_host(ctx, st, ctx->io[4].p, nodes_out, n_leaves, ctx->digest_bytes))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
@@ -1466,6 +1508,7 @@ int wf_trace_commit_sharded_dev(wf_comm *c, const wf_params *p, const void *d_tr
     if (!c) return fail(WF_ERR_ARG, "comm is null");
     int rc = check_params(p, false);
     if (rc) return rc;
+    if ((rc = check_blake3_only(p, "wf_trace_commit_sharded_dev"))) return rc;
     if (!d_trace || !d_lde_shard || !d_leaves || !d_nodes || !d_top) return fail(WF_ERR_ARG, "null device buffer");
     uint32_t c0, cn;
     rc = wf_shard_cosets(1u << p->log2_blowup, (uint32_t)c->rank, (uint32_t)c->world, &c0, &cn);
@@ -1510,13 +1553,13 @@ bool path_dense_column_ok(const wf_params *p) {
 bool path_dense_matrix_ok(const wf_params *p) { return dense_matrix_ok(p); }
 
 int path_hash_rows(wf_ctx *ctx, hipStream_t st, uint32_t field, const void *lde, uint64_t trace_elems, uint64_t n_rows,
-                   uint32_t row_width, uint32_t epr, uint32_t n_traces, void *leaves, uint32_t digest_bytes) {
-    return field == WF_FIELD_F64 ? run_hash_rows<F64>(ctx, st, lde, trace_elems, n_rows, row_width, epr, n_traces, leaves, digest_bytes / 4)
-                                 : run_hash_rows<F128>(ctx, st, lde, trace_elems, n_rows, row_width, epr, n_traces, leaves, digest_bytes / 4);
+                   uint32_t row_width, uint32_t epr, uint32_t n_traces, void *leaves, uint32_t digest_bytes, uint32_t hasher) {
+    return field == WF_FIELD_F64 ? run_hash_rows<F64>(ctx, st, lde, trace_elems, n_rows, row_width, epr, n_traces, leaves, digest_bytes / 4, hasher)
+                                 : run_hash_rows<F128>(ctx, st, lde, trace_elems, n_rows, row_width, epr, n_traces, leaves, digest_bytes / 4, hasher);
 }
 
-int path_merkle(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes, uint32_t digest_bytes) {
-    return run_merkle(ctx, st, leaves, n_leaves, nodes, digest_bytes / 4);
+int path_merkle(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes, uint32_t digest_bytes, uint32_t hasher) {
+    return run_merkle(ctx, st, leaves, n_leaves, nodes, digest_bytes / 4, hasher);
 }
 
 int path_digests_to_host(wf_ctx *ctx, hipStream_t st, const void *d_slots, void *host, size_t n, uint32_t digest_bytes) {

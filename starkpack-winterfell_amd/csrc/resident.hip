@@ -780,6 +780,7 @@ int wf_trace_commit_sharded_resident(wf_comm *comm, const wf_params *p, const vo
     if (!comm || !out) return fail(WF_ERR_ARG, "null argument");
     int rc = check_params(p, false);
     if (rc) return rc;
+    if ((rc = check_blake3_only(p, "wf_trace_commit_sharded_resident"))) return rc;
     if (!trace_cols) return fail(WF_ERR_ARG, "column pointer array is null");
     uint32_t c0, per;
     rc = wf_shard_cosets(1u << p->log2_blowup, (uint32_t)comm->rank, (uint32_t)comm->world, &c0, &per);
