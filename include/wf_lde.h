@@ -2,7 +2,7 @@
  * wf_lde.h -- C ABI of libwf_lde.so: MI355X (gfx950) implementation of the winter-prover hot path
  *   trace / constraint low-degree extension (radix-2 NTT over the f64 and f128 base fields, coset evaluation)
  *   + BLAKE3-256 Merkle commitment of the extended rows, including STARKPack's combined-row commitment
- *   (or Sha3_256, the reference's other byte-digest hasher: enum wf_hasher).
+ *   (or Sha3_256, the reference's other byte-digest hasher, or Rp64_256, its Rescue Prime hasher over f64: enum wf_hasher).
  *
  * The reference (Rust) has no FFI layer; the seam these entry points replace is the pair of provided methods
  *   Prover::build_trace_commitment       /root/reference/prover/src/lib.rs:615-670
@@ -39,12 +39,18 @@ typedef struct wf_ctx wf_ctx;
 enum wf_field { WF_FIELD_F64 = 1, WF_FIELD_F128 = 2 };
 /* The reference's `H: ElementHasher` type parameter (Prover::HashFn): BLAKE3 (crypto/src/hash/blake/mod.rs; Blake3_256 or
  * Blake3_192 by digest_bytes) or Sha3_256 (crypto/src/hash/sha/mod.rs:17-57; 32-byte digests only).  With Sha3_256 a leaf is
- * SHA3-256 of the row's canonical bytes and nodes[i] = SHA3-256(nodes[2i] || nodes[2i+1]); every layout is unchanged. */
-enum wf_hasher { WF_HASH_BLAKE3 = 0, WF_HASH_SHA3_256 = 1 };
+ * SHA3-256 of the row's canonical bytes and nodes[i] = SHA3-256(nodes[2i] || nodes[2i+1]); every layout is unchanged.
+ * Ids 0..15 are byte-digest hashers, element-digest hashers start at 16.  Rp64_256 (crypto/src/hash/rescue/rp64_256/mod.rs) is
+ * an ElementHasher over the f64 field: WF_FIELD_F64 only (any ext_degree: extension elements are hashed as their base
+ * elements, and the element count the sponge starts from is the base-element count), 32-byte digests only.  A digest is
+ * ElementDigest::as_bytes -- its four elements as canonical little-endian u64 -- in every array, slot, root and proof;
+ * nodes[0] is the all-zero digest.  Digest words a caller hands in (wf_merkle_build*) are read as BaseElement::new reads
+ * them (any u64, reduced mod p); digests the library writes are canonical.  WF_FIELD_F128 with Rp64_256 is WF_ERR_FIELD. */
+enum wf_hasher { WF_HASH_BLAKE3 = 0, WF_HASH_SHA3_256 = 1, WF_HASH_RP64_256 = 16 };
 
 enum wf_status {
     WF_OK = 0,
-    WF_ERR_FIELD = -10,        /* unknown field id */
+    WF_ERR_FIELD = -10,        /* unknown field id; WF_FIELD_F128 with the Rp64_256 hasher */
     WF_ERR_EXTENSION = -11,    /* ext_degree not in {1,2,3}, or 3 over f128 (f128/mod.rs:296-314) */
     WF_ERR_TRACE_LENGTH = -12, /* trace length < 8 or not a power of two (air/src/air/trace_info.rs:35) */
     WF_ERR_BLOWUP = -13,       /* blowup not a power of two in [2,128] (air/src/options.rs:19-20) */
@@ -56,8 +62,8 @@ enum wf_status {
     WF_ERR_ARG = -19,          /* null pointer or other malformed argument */
     WF_ERR_BUSY = -20,         /* the context is inside a call of another thread (one call at a time per wf_ctx) */
     WF_ERR_HIP = -30,          /* HIP runtime failure (no device, out of memory, launch failure) */
-    WF_ERR_DIGEST = -31,       /* digest_bytes is neither 32 (Blake3_256) nor 24 (Blake3_192); unknown hasher id; Sha3_256
-                                * with digest_bytes other than 32 (wf_params, or the context's pair of setters) */
+    WF_ERR_DIGEST = -31,       /* digest_bytes is neither 32 (Blake3_256) nor 24 (Blake3_192); unknown hasher id; Sha3_256 or
+                                * Rp64_256 with digest_bytes other than 32 (wf_params, or the context's pair of setters) */
     WF_ERR_COMM = -32          /* RCCL (or caller-supplied transport) failure, librccl.so.1 not loadable */
 };
 
@@ -76,7 +82,8 @@ typedef struct wf_params {
                               * reference's Vec<ByteDigest<N>>; DEVICE arrays (d_leaves, d_nodes of the *_dev forms, resident
                               * handles) are always 32-byte slots with the digest in front and zeros behind; root_out[32]
                               * is the digest zero-padded (Digest::as_bytes, crypto/src/hash/mod.rs:107-113) */
-    uint32_t hasher;         /* enum wf_hasher; 0 = BLAKE3 (the field was `reserved, must be 0`: same offset and size) */
+    uint32_t hasher;         /* enum wf_hasher; 0 = BLAKE3 (the field was `reserved, must be 0`: same offset and size),
+                              * 1 = Sha3_256, 16 = Rp64_256 (field f64 only) */
     uint8_t domain_offset[16]; /* StarkDomain::offset() as a canonical little-endian integer (7 for f64, 3 for f128) */
 } wf_params;
 
@@ -102,10 +109,11 @@ int wf_ctx_release_cached(wf_ctx *ctx);
  * functions (the reference's `H: ElementHasher` type parameter, one per Prover): 32 = Blake3_256 (default), 24 =
  * Blake3_192.  Layout rules as for wf_params::digest_bytes. */
 int wf_ctx_set_digest_bytes(wf_ctx *ctx, uint32_t digest_bytes);
-/* The other half of that hasher: WF_HASH_BLAKE3 (default) or WF_HASH_SHA3_256, for the same entry points (wf_hash_rows,
+/* The other half of that hasher: WF_HASH_BLAKE3 (default), WF_HASH_SHA3_256 or WF_HASH_RP64_256, for the same entry points (wf_hash_rows,
  * wf_merkle_build, wf_merkle_build_dev, wf_fri_layer_commit*, the layers and the remainder digest of a wf_fri_prover).
- * The pair must stay consistent: Sha3_256 on a 24-byte context, or 24 bytes on a Sha3_256 context, is refused with
- * WF_ERR_DIGEST and changes nothing (go through BLAKE3 / 32 bytes).  Commitments carry theirs in wf_params::hasher. */
+ * The pair must stay consistent: Sha3_256 or Rp64_256 on a 24-byte context, or 24 bytes on such a context, is refused with
+ * WF_ERR_DIGEST and changes nothing (go through BLAKE3 / 32 bytes).  Commitments carry theirs in wf_params::hasher.
+ * On an Rp64_256 context wf_hash_rows and the wf_fri_* entry points refuse WF_FIELD_F128 with WF_ERR_FIELD. */
 int wf_ctx_set_hasher(wf_ctx *ctx, uint32_t hasher);
 /* Diagnostic (needs no device): the digit passes the commitment path uses for a transform of 2^log2_n rows over
  * n_segments segments (a segment = 8 f64 / 4 f128 base columns); returns the number of passes (<= 4), digits_out[i] =

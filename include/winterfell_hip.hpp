@@ -248,6 +248,9 @@ struct Blake3_256 {
 struct Sha3_256 {
     static constexpr uint32_t ID = WF_HASH_SHA3_256;
 };
+struct Rp64_256 {  // f64 matrices only; a digest is ElementDigest::as_bytes (four canonical little-endian u64)
+    static constexpr uint32_t ID = WF_HASH_RP64_256;
+};
 
 class Prover {
   public:

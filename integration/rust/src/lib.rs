@@ -61,9 +61,16 @@ impl WfField for f128::BaseElement {
 /// (`ByteDigest<N>`, `crypto/src/hash/mod.rs:84-85`): `Blake3_256` (32) and `Blake3_192` (24: the BLAKE3 output truncated,
 /// 48-byte merges, `crypto/src/hash/blake/mod.rs:68-114`) and `Sha3_256` (32, `crypto/src/hash/sha/mod.rs:17-57`).  Host
 /// arrays of digests hold `DIGEST_BYTES` per entry; `HASHER` is the `enum wf_hasher` id that goes into `wf_params::hasher`.
+///
+/// `Rp64_256` (Rescue Prime over the f64 field, `crypto/src/hash/rescue/rp64_256/mod.rs`; `WF_HASH_RP64_256` = 16, f64 traces
+/// only) has an element digest: the library reads and writes it as `ElementDigest::as_bytes` -- four canonical
+/// little-endian `u64` -- while the type holds four `BaseElement`s in their internal form.  `digests_from_library` turns
+/// an array the library has just filled into values of the digest type (nothing to do for a byte digest); every wrapper
+/// below calls it on the leaves and nodes it hands to `MerkleTree::from_raw_parts` / `BatchMerkleProof`.
 pub trait WfHasher: ElementHasher + Hasher {
     const DIGEST_BYTES: u32;
     const HASHER: u32;
+    fn digests_from_library(_digests: &mut [Self::Digest]) {}
 }
 impl<B: StarkField> WfHasher for crypto::hashers::Blake3_256<B> {
     const DIGEST_BYTES: u32 = 32;
@@ -76,6 +83,19 @@ impl<B: StarkField> WfHasher for crypto::hashers::Blake3_192<B> {
 impl<B: StarkField> WfHasher for crypto::hashers::Sha3_256<B> {
     const DIGEST_BYTES: u32 = 32;
     const HASHER: u32 = 1;
+}
+
+impl WfHasher for crypto::hashers::Rp64_256 {
+    const DIGEST_BYTES: u32 = 32;
+    const HASHER: u32 = 16;
+    fn digests_from_library(digests: &mut [Self::Digest]) {
+        for d in digests.iter_mut() {
+            // 32 bytes of ElementDigest::as_bytes sit where the value will be: read them through the type's own
+            // Deserializable impl (BaseElement::new on each little-endian u64, rp64_256/digest.rs:58-68)
+            let bytes: [u8; 32] = unsafe { core::ptr::read(d as *const Self::Digest as *const [u8; 32]) };
+            *d = <Self::Digest as Deserializable>::read_from_bytes(&bytes).expect("digest");
+        }
+    }
 }
 
 // CONTEXT
@@ -185,6 +205,8 @@ where
         )
     };
     check(rc).expect("failed to build trace commitment"); // the reference panics on the same preconditions
+    H::digests_from_library(&mut leaves);
+    H::digests_from_library(&mut nodes);
 
     let trace_ldes = ldes
         .into_iter()
@@ -222,6 +244,8 @@ where
         )
     };
     check(rc).expect("failed to build constraint commitment");
+    H::digests_from_library(&mut leaves);
+    H::digests_from_library(&mut nodes);
 
     let evaluations = RowMatrix::from_raw_parts(lde, row_width, data.num_base_cols());
     let commitment = MerkleTree::from_raw_parts(nodes, leaves).expect("failed to construct constraint Merkle tree");
@@ -342,6 +366,8 @@ where
             )
         };
         check(rc).expect("failed to query the commitment"); // TooFewLeafIndexes / duplicates / out of range, as the reference
+        H::digests_from_library(&mut leaves);
+        H::digests_from_library(&mut flat[..n_nodes]);
         let mut nodes = Vec::with_capacity(n_vec);
         let mut k = 0;
         for &cnt in &counts[..n_vec] {

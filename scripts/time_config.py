@@ -1,13 +1,23 @@
 """Times the device-buffer form of the trace commitment for an arbitrary configuration (bring-up / tuning aid).
-    python scripts/time_config.py <field 1|2> <ext> <log2 R> <log2 blowup> <n_cols> <n_traces> [hasher 0|1]
-(hasher: 0 = BLAKE3, 1 = Sha3_256)"""
+    python scripts/time_config.py <field 1|2> <ext> <log2 R> <log2 blowup> <n_cols> <n_traces> [hasher id] [--hasher NAME|id]
+(hasher: 0 / blake3 = BLAKE3, 1 / sha3 = Sha3_256, 16 / rp64 = Rp64_256; the profile marks split the time into the
+transform, "hash_rows" and "merkle")"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import starkpack_winterfell_amd.capi as capi
 
-field, ext, logR, logB, n_cols, n_traces = (int(x) for x in sys.argv[1:7])
-hasher = int(sys.argv[7]) if len(sys.argv) > 7 else capi.BLAKE3
+HASHERS = {"blake3": capi.BLAKE3, "sha3": capi.SHA3_256, "rp64": capi.RP64_256}
+argv = sys.argv[1:]
+hasher = capi.BLAKE3
+if "--hasher" in argv:
+    at = argv.index("--hasher")
+    name = argv[at + 1].lower()
+    hasher = HASHERS[name] if name in HASHERS else int(name)
+    del argv[at:at + 2]
+elif len(argv) > 6:
+    hasher = int(argv[6])
+field, ext, logR, logB, n_cols, n_traces = (int(x) for x in argv[:6])
 dev = torch.device("cuda", 0)
 ctx = capi.Context(0)
 w = 1 if field == 1 else 2

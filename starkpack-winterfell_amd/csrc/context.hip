@@ -295,13 +295,33 @@ int check_params(const wf_params *p, bool constraint) {
     if (p->n_traces < 1 || (constraint && p->n_traces != 1)) return fail(WF_ERR_TRACES, "invalid number of traces %u", p->n_traces);
     if (p->digest_bytes != 32 && p->digest_bytes != 24)
         return fail(WF_ERR_DIGEST, "digest_bytes must be 32 (Blake3_256) or 24 (Blake3_192), got %u", p->digest_bytes);
-    if (p->hasher > WF_HASH_SHA3_256) return fail(WF_ERR_DIGEST, "unknown hasher id %u (0 = BLAKE3, 1 = Sha3_256)", p->hasher);
-    if (p->hasher == WF_HASH_SHA3_256 && p->digest_bytes != 32)
-        return fail(WF_ERR_DIGEST, "Sha3_256 has 32-byte digests, got digest_bytes %u", p->digest_bytes);
+    int hrc = check_hasher_pair(p->hasher, p->digest_bytes);
+    if (hrc) return hrc;
+    if ((hrc = check_hasher_field(p->hasher, p->field))) return hrc;
     u128 off;
     memcpy(&off, p->domain_offset, 16);
     const u128 mod = p->field == WF_FIELD_F64 ? (u128)F64::P : F128::P();
     if (off == 0 || off >= mod) return fail(WF_ERR_OFFSET, "domain offset must be a non-zero field element");
+    return 0;
+}
+
+static const char *hasher_name(uint32_t hasher) {
+    return hasher == WF_HASH_BLAKE3 ? "BLAKE3" : hasher == WF_HASH_SHA3_256 ? "Sha3_256" : hasher == WF_HASH_RP64_256 ? "Rp64_256" : nullptr;
+}
+
+// a known hasher id, and a digest size that hasher has (BLAKE3: 32 or 24, the others 32)
+int check_hasher_pair(uint32_t hasher, uint32_t digest_bytes) {
+    if (!hasher_name(hasher))
+        return fail(WF_ERR_DIGEST, "unknown hasher id %u (0 = BLAKE3, 1 = Sha3_256, 16 = Rp64_256)", hasher);
+    if (hasher != WF_HASH_BLAKE3 && digest_bytes != 32)
+        return fail(WF_ERR_DIGEST, "%s has 32-byte digests, got digest_bytes %u", hasher_name(hasher), digest_bytes);
+    return 0;
+}
+
+// an element-digest hasher hashes elements of its own field only
+int check_hasher_field(uint32_t hasher, uint32_t field) {
+    if (hasher == WF_HASH_RP64_256 && field != WF_FIELD_F64)
+        return fail(WF_ERR_FIELD, "Rp64_256 hashes elements of the f64 field only (field id %u)", field);
     return 0;
 }
 
@@ -445,8 +465,9 @@ int wf_ctx_set_digest_bytes(wf_ctx *ctx, uint32_t digest_bytes) {
     if (!ctx) return fail(WF_ERR_ARG, "ctx is null");
     if (digest_bytes != 32 && digest_bytes != 24)
         return fail(WF_ERR_DIGEST, "digest_bytes must be 32 (Blake3_256) or 24 (Blake3_192), got %u", digest_bytes);
-    if (digest_bytes != 32 && ctx->hasher == WF_HASH_SHA3_256)
-        return fail(WF_ERR_DIGEST, "the context hashes with Sha3_256, which has 32-byte digests (got digest_bytes %u)", digest_bytes);
+    if (digest_bytes != 32 && ctx->hasher != WF_HASH_BLAKE3)
+        return fail(WF_ERR_DIGEST, "the context hashes with %s, which has 32-byte digests (got digest_bytes %u)",
+                    hasher_name(ctx->hasher), digest_bytes);
     WF_ENTER(ctx, nullptr);
     ctx->digest_bytes = digest_bytes;
     return 0;
@@ -454,9 +475,8 @@ int wf_ctx_set_digest_bytes(wf_ctx *ctx, uint32_t digest_bytes) {
 
 int wf_ctx_set_hasher(wf_ctx *ctx, uint32_t hasher) {
     if (!ctx) return fail(WF_ERR_ARG, "ctx is null");
-    if (hasher > WF_HASH_SHA3_256) return fail(WF_ERR_DIGEST, "unknown hasher id %u (0 = BLAKE3, 1 = Sha3_256)", hasher);
-    if (hasher == WF_HASH_SHA3_256 && ctx->digest_bytes != 32)
-        return fail(WF_ERR_DIGEST, "Sha3_256 has 32-byte digests, the context is set to %u", ctx->digest_bytes);
+    const int rc = check_hasher_pair(hasher, ctx->digest_bytes);  // (the context's digest size: nothing changes on refusal)
+    if (rc) return rc;
     WF_ENTER(ctx, nullptr);
     ctx->hasher = hasher;
     return 0;

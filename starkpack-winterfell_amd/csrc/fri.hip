@@ -11,6 +11,8 @@ using namespace wf;
 static int check_fri_args(wf_ctx *ctx, uint32_t field, uint32_t ext, size_t n, uint32_t folding, uint32_t *logn) {
     if (!ctx) return fail(WF_ERR_ARG, "ctx is null");
     if (field != WF_FIELD_F64 && field != WF_FIELD_F128) return fail(WF_ERR_FIELD, "unknown field id %u", field);
+    int hrc = check_hasher_field(ctx->hasher, field);  // (the layers and the remainder are hashed with the context's hasher)
+    if (hrc) return hrc;
     if (ext < 1 || ext > 3 || (field == WF_FIELD_F128 && ext == 3)) return fail(WF_ERR_EXTENSION, "unsupported extension degree %u", ext);
     if (folding != 2 && folding != 4 && folding != 8 && folding != 16)
         return fail(WF_ERR_ARG, "folding factor %u is not supported", folding);  // fri/src/prover/mod.rs:178-185
@@ -478,6 +480,8 @@ int wf_fri_prover_set_remainder(wf_fri_prover *pr, void *remainder_out, size_t c
     if (!pr || !remainder_out || !len_out || !commitment_out) return fail(WF_ERR_ARG, "null argument");
     if (!pr->evals) return fail(WF_ERR_ARG, "no evaluations: call wf_fri_prover_begin first");
     if (pr->pending) return fail(WF_ERR_ARG, "the committed layer has not been folded yet");
+    int hrc = check_hasher_field(pr->ctx->hasher, pr->field);  // before the remainder is interpolated: nothing changes on refusal
+    if (hrc) return hrc;
     const size_t len = pr->n / pr->blowup;
     if (len == 0) return fail(WF_ERR_BLOWUP, "fewer evaluations (%zu) than the blowup factor (%u)", pr->n, pr->blowup);
     if (len > capacity) return fail(WF_ERR_ARG, "remainder has %zu coefficients, buffer holds %zu", len, capacity);

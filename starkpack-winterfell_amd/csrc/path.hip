@@ -5,6 +5,7 @@
 
 #include "kernels.hpp"
 #include "keccak_kernels.hpp"
+#include "rescue_kernels.hpp"
 #include "seg_kernels.hpp"
 #include "col_kernels.hpp"
 #include "fri_kernels.hpp"
@@ -699,6 +700,16 @@ static int run_hash_rows(wf_ctx *ctx, hipStream_t st, const void *lde, uint64_t 
         HIP_TRY(hipGetLastError());
         return 0;
     }
+    if (hasher == WF_HASH_RP64_256) {  // likewise one lane per row; the sponge takes the stored (Montgomery) elements as they are
+        if constexpr (F::FIELD_ID == 1) {
+            if (grid > 0x7FFFFFFFull) return fail(WF_ERR_ARG, "too many rows for one launch");
+            hipLaunchKernelGGL(k_rp64_hash_rows, dim3((uint32_t)grid), dim3(threads), 0, st, h);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        } else {
+            return fail(WF_ERR_FIELD, "Rp64_256 hashes elements of the f64 field only");
+        }
+    }
     const uint64_t row_bytes = (uint64_t)n_traces * epr * F::BYTES;
     if (row_bytes <= 1024) {  // single BLAKE3 chunk: one lane per row, no subtree stack
         hipLaunchKernelGGL(k_hash_rows<F>, dim3((uint32_t)grid), dim3(threads), 0, st, h);
@@ -800,10 +811,45 @@ static int run_merkle_sha3(hipStream_t st, const void *leaves, uint64_t n_leaves
     return 0;
 }
 
+// Rp64_256 tree: one lane per parent (rp::permute) while a level has at least 2^RP64_LEVEL_MIN_LOG parents, then the
+// lane-form subtree kernel (16 lanes per parent, rp::permute_lane), up to RP64_SUBTREE_LEVELS levels per launch.  The switch
+// is measured (docs/EXPERIMENTS.md "Rp64_256", scripts/rescue_bench.hip): a level of up to 2^16 parents costs one
+// permutation's latency with one lane per parent (0.33 ms), the lane form's latency is a ninth of that and its throughput
+// 73 %, so it wins up to 2^15 parents.  A pure kernel sequence like the other trees.
+static constexpr uint32_t RP64_LEVEL_MIN_LOG = 16;
+static int run_merkle_rp64(hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes) {
+    const uint64_t *children = (const uint64_t *)leaves;
+    uint64_t n_children = n_leaves;
+    while (n_children > 1) {
+        const uint64_t n_par = n_children >> 1;
+        if (n_par >= ((uint64_t)1 << RP64_LEVEL_MIN_LOG)) {
+            const uint32_t threads = 256;
+            const uint64_t grid = (n_par + threads - 1) / threads;
+            if (grid > 0x7FFFFFFFull) return fail(WF_ERR_ARG, "too many leaves for one launch");
+            hipLaunchKernelGGL(k_rp64_merkle_level, dim3((uint32_t)grid), dim3(threads), 0, st, (const ulonglong2 *)children,
+                               (ulonglong2 *)nodes + n_par * 2, n_par);
+            HIP_TRY(hipGetLastError());
+            n_children = n_par;
+        } else {
+            uint32_t total_levels = 0;
+            for (uint64_t t = n_children; t > 1; t >>= 1) total_levels++;
+            const uint32_t levels = std::min<uint32_t>(RP64_SUBTREE_LEVELS, total_levels);
+            const uint64_t grid = (n_par + RP64_SUBTREE_SPAN - 1) / RP64_SUBTREE_SPAN;
+            hipLaunchKernelGGL(k_rp64_merkle_subtree, dim3((uint32_t)grid), dim3(RP64_SUBTREE_THREADS), 0, st, children,
+                               (uint64_t *)nodes, n_children, levels);
+            HIP_TRY(hipGetLastError());
+            n_children >>= levels;
+        }
+        children = (const uint64_t *)nodes + n_children * 4;  // that level lives at nodes[n .. 2n)
+    }
+    return 0;
+}
+
 // dw: digest words -- 8 = Blake3_256, 6 = Blake3_192 (48-byte merge inputs; the slots' last two words are zeros)
 static int run_merkle(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes, uint32_t dw = 8,
                       uint32_t hasher = WF_HASH_BLAKE3) {
     if (hasher == WF_HASH_SHA3_256) return run_merkle_sha3(st, leaves, n_leaves, nodes);
+    if (hasher == WF_HASH_RP64_256) return run_merkle_rp64(st, leaves, n_leaves, nodes);
     return dw == 6 ? run_merkle_dw<6>(ctx, st, leaves, n_leaves, nodes) : run_merkle_dw<8>(ctx, st, leaves, n_leaves, nodes);
 }
 
@@ -1378,6 +1424,8 @@ int wf_fft_evaluate_poly_with_offset(wf_ctx *ctx, uint32_t field, uint32_t ext, 
 int wf_hash_rows(wf_ctx *ctx, uint32_t field, const void *rows, size_t n_rows, size_t row_elems, uint8_t *digests_out) {
     if (!ctx) return fail(WF_ERR_ARG, "ctx is null");
     if (field != WF_FIELD_F64 && field != WF_FIELD_F128) return fail(WF_ERR_FIELD, "unknown field id %u", field);
+    int hrc = check_hasher_field(ctx->hasher, field);
+    if (hrc) return hrc;
     if (!digests_out || (!rows && n_rows * row_elems)) return fail(WF_ERR_ARG, "null argument");
     if (n_rows == 0) return 0;
     HIP_TRY(hipSetDevice(ctx->device));

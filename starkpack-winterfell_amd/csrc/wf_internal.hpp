@@ -87,7 +87,7 @@ struct wf_ctx {
     // the hasher of the entry points that take no wf_params (wf_hash_rows, wf_merkle_build*, wf_fri_*): 32 = Blake3_256
     // (default), 24 = Blake3_192; wf_ctx_set_digest_bytes.  Commitments carry theirs in wf_params::digest_bytes.
     uint32_t digest_bytes = 32;
-    uint32_t hasher = WF_HASH_BLAKE3;  // wf_ctx_set_hasher; WF_HASH_SHA3_256 only together with digest_bytes == 32
+    uint32_t hasher = WF_HASH_BLAKE3;  // wf_ctx_set_hasher; a hasher other than BLAKE3 only together with digest_bytes == 32
     DevBuf pack_tmp;  // 24-byte digests on their way between host arrays and the device's 32-byte slots
     hipStream_t stream = nullptr;
     // key: (field, logN, kind, aux, offset lo, offset hi); kind 0 = forward root, 1 = inverse root,
@@ -205,6 +205,8 @@ int ensure(wf_ctx *ctx, DevBuf &b, size_t bytes);
 int upload_columns(wf_ctx *ctx, void *dst, const void *const *cols, size_t n, size_t colb, hipStream_t st);
 int download_columns(wf_ctx *ctx, void *const *cols, const void *src, size_t n, size_t colb, hipStream_t st);
 int check_params(const wf_params *p, bool constraint);
+int check_hasher_pair(uint32_t hasher, uint32_t digest_bytes);  // WF_ERR_DIGEST: unknown id, or a digest size the hasher lacks
+int check_hasher_field(uint32_t hasher, uint32_t field);        // WF_ERR_FIELD: Rp64_256 with a field other than f64
 int check_blake3_only(const wf_params *p, const char *what);  // the multi-GPU entry points: WF_ERR_ARG for another hasher
 
 // ------------------------------------------------------------------------------------------------- comm.hip
@@ -248,7 +250,7 @@ int path_constraint_commit(wf_ctx *ctx, const wf_params *p, const void *d_polys,
 bool path_dense_column_ok(const wf_params *p);
 bool path_dense_matrix_ok(const wf_params *p);
 // (digest_bytes: 32 or 24; device leaves / nodes are 32-byte slots either way, a 24-byte digest in the first 24 bytes;
-// hasher: enum wf_hasher -- Sha3_256 goes to the kernels of keccak_kernels.hpp)
+// hasher: enum wf_hasher -- Sha3_256 goes to the kernels of keccak_kernels.hpp, Rp64_256 to those of rescue_kernels.hpp)
 int path_hash_rows(wf_ctx *ctx, hipStream_t st, uint32_t field, const void *lde, uint64_t trace_elems, uint64_t n_rows,
                    uint32_t row_width, uint32_t epr, uint32_t n_traces, void *leaves, uint32_t digest_bytes, uint32_t hasher);
 int path_merkle(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes, uint32_t digest_bytes,

@@ -1,0 +1,159 @@
+"""CPU: the Rp64_256 of csrc/rescue_dev.hpp (what the Rescue row and tree kernels run) against tests/rp64_util.py, the
+restatement of the function on Python integers, and against the reference's one literal known answer
+(tests/golden/rp64_256_kat.json).  Built with plain g++: the functions are __host__ __device__.  Both forms of the
+permutation go through every state: `P` is the one-lane-per-permutation code, `Q` the host side of the lane form."""
+import ctypes
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import rp64_util as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+P = R.P
+LENGTHS = [1, 7, 8, 9, 15, 16, 17, 255]
+EDGES = [0, 1, P - 1, 2**32 - 1]
+
+
+def _golden(name):
+    return json.load(open(os.path.join(ROOT, "tests", "golden", name)))
+
+
+def _build(tmp_path, extra=()):
+    exe = str(tmp_path / "test_rescue_host")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", *extra, "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-o", exe,
+                           os.path.join(ROOT, "tests", "cpp", "test_rescue_host.cpp")])
+    return exe
+
+
+def _edge_states():
+    """States built from 0, 1, p - 1 and 2^32 - 1 (the carry edges of the reduction): each value everywhere, then the four
+    values rotated through the twelve places."""
+    states = [[e] * 12 for e in EDGES]
+    for k in range(4):
+        states.append([EDGES[(i + k) % 4] for i in range(12)])
+    states.append([P - 1] * 11 + [0])
+    return states
+
+
+def _requests():
+    """(request line, expected list of integers) pairs; the expected side is Python integers only.  ~150 permutations."""
+    rng = np.random.default_rng(17)
+    out = []
+    kat = _golden("rp64_256_kat.json")
+    for op in "PQ":
+        out.append((op, kat["input"], kat["expected"]))
+    for s in _edge_states() + [[int(x) for x in rng.integers(0, P, size=12, dtype=np.uint64)] for _ in range(3)]:
+        want = R.permute(s)
+        for op in "PQ":
+            out.append((op, s, want))
+    for n in LENGTHS:
+        e = [int(x) for x in rng.integers(0, P, size=n, dtype=np.uint64)]
+        out.append(("H", e, R.hash_elements(e)))
+    for n in (1, 8, 9, 16):  # the same lengths on edge values: additions that wrap and that land in [p, 2^64)
+        e = [EDGES[(i + n) % 4] for i in range(n)]
+        out.append(("H", e, R.hash_elements(e)))
+        e = [P - 1] * n
+        out.append(("H", e, R.hash_elements(e)))
+    # merge, canonical words; words >= p (read as BaseElement::new reads them: reduced); all-zero digests
+    merges = [[int(x) for x in rng.integers(0, P, size=8, dtype=np.uint64)] for _ in range(2)]
+    merges += [[0] * 8, [P - 1] * 8, [P, P + 1, 2**64 - 1, 2**64 - 2**32, 0, 1, P - 1, 2**32 - 1]]
+    for m in merges:
+        want = R.hash_elements([x % P for x in m])
+        assert R.digest_bytes(want) == R.merge(b"".join(int(x % P).to_bytes(8, "little") for x in m[:4]),
+                                                b"".join(int(x % P).to_bytes(8, "little") for x in m[4:]))
+        out.append(("M", m, want))
+        out.append(("L", m, want))
+        out.append(("H", [x % P for x in m], want))  # merge(a, b) == hash_elements(a || b)
+    return out
+
+
+def _ask(exe, lines, env=None):
+    res = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=120, env=env)
+    assert res.returncode == 0, res.stdout + res.stderr
+    return [[int(x) for x in l.split()] for l in res.stdout.splitlines()]
+
+
+_CASES = None
+
+
+def _run(exe, env=None):
+    global _CASES
+    if _CASES is None:
+        _CASES = _requests()  # the Python reference once, shared by the plain and the sanitizer run
+    got = _ask(exe, [" ".join([op] + [str(x) for x in words]) for op, words, _ in _CASES], env)
+    assert len(got) == len(_CASES)
+    for (op, words, want), g in zip(_CASES, got):
+        assert g == want, f"{op} request of {len(words)} words"
+    # the element count is part of the hash: a trailing zero element changes the digest
+    a, b = _ask(exe, ["H 5", "H 5 0"], env)
+    assert a != b and a == R.hash_elements([5]) and b == R.hash_elements([5, 0])
+
+
+def test_rp64_256_matches_the_python_reference(tmp_path):
+    _run(_build(tmp_path))
+
+
+def test_rp64_256_under_address_and_ub_sanitizers(tmp_path):
+    """The same stand-alone program with -fsanitize=address,undefined (nothing is preloaded: it has its own main)."""
+    try:
+        exe = _build(tmp_path, ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"))
+    except subprocess.CalledProcessError:
+        pytest.skip("this g++ has no sanitizer runtime")
+    _run(exe, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+
+
+def test_header_tables_are_the_fixture_in_montgomery_form(tmp_path):
+    prm = _golden("rp64_256_params.json")
+    (t,) = _ask(_build(tmp_path), ["T"])
+    assert len(t) == 84 + 84 + 12
+    flat1 = [x for row in prm["ark1"] for x in row]
+    flat2 = [x for row in prm["ark2"] for x in row]
+    assert t[:84] == [x * 2**64 % P for x in flat1]
+    assert t[84:168] == [x * 2**64 % P for x in flat2]
+    assert t[168:] == prm["mds_row"]
+    assert prm["alpha"] == 7 and prm["alpha"] * prm["inv_alpha"] % (P - 1) == 1
+
+
+def test_python_reference_reproduces_the_known_answer():
+    kat = _golden("rp64_256_kat.json")
+    assert R.permute(kat["input"]) == kat["expected"]
+    # helpers of the GPU tests: a tree of four leaves by hand, the sampled set within its budget
+    leaves = np.arange(4 * 32, dtype=np.uint8).reshape(4, 32)
+    nodes = R.merkle_nodes(leaves)
+    assert not nodes[0].any()
+    assert bytes(nodes[1]) == R.merge(R.merge(bytes(leaves[0]), bytes(leaves[1])), R.merge(bytes(leaves[2]), bytes(leaves[3])))
+    R.check_tree_sampled(nodes, leaves, [1, 2, 3])
+    for log_n in (9, 15, 16, 17):
+        idx = R.sample_indices(1 << log_n, spans=(64,))
+        assert len(idx) == len(set(idx)) <= 2048 and all(1 <= i < (1 << log_n) for i in idx)
+        assert set(range(1, 256)) <= set(idx)
+    # Montgomery residue -> canonical: 2^64 mod p is the residue of one
+    assert R.canonical(np.array([2**64 % P], dtype=np.uint64)) == [1]
+
+
+def test_params_check_knows_rp64_256(capi):
+    lib = capi.load()
+    assert capi.RP64_256 == 16
+
+    def check(**kw):
+        field = kw.pop("field", capi.F64)
+        return lib.wf_params_check(ctypes.byref(capi.make_params(field, 1, 10, 3, 8, 1, **kw)), 0)
+
+    assert check(hasher=capi.RP64_256) == 0
+    for ext in (2, 3):
+        assert lib.wf_params_check(ctypes.byref(capi.make_params(capi.F64, ext, 10, 3, 2, 1, hasher=capi.RP64_256)), 0) == 0
+    assert check(field=capi.F128, hasher=capi.RP64_256) == -10
+    assert b"Rp64_256" in lib.wf_last_error()
+    assert check(digest_bytes=24, hasher=capi.RP64_256) == -31
+    assert b"Rp64_256" in lib.wf_last_error()
+    for unknown in (2, 15, 17):
+        assert check(hasher=unknown) == -31
+        assert b"hasher" in lib.wf_last_error()
+    # the byte-digest hashers are unchanged
+    assert check(hasher=capi.BLAKE3) == 0 and check(hasher=capi.BLAKE3, digest_bytes=24) == 0
+    assert check(hasher=capi.SHA3_256) == 0 and check(hasher=capi.SHA3_256, digest_bytes=24) == -31
+    assert check(field=capi.F128, hasher=capi.SHA3_256) == 0
