@@ -7,7 +7,7 @@ LIB = os.path.join(CSRC, "libwf_lde.so")
 
 
 def build(force: bool = False) -> str:
-    args = ["make", "-j8", "-C", CSRC, "libwf_lde.so", "libwf_yardstick.so"]
+    args = ["make", "-j8", "-C", CSRC, "libwf_lde.so", "libwf_yardstick.so", "libwf_field_probe.so"]
     if force:
         args.insert(1, "-B")
     subprocess.check_call(args, stdout=subprocess.DEVNULL)
@@ -17,6 +17,11 @@ def build(force: bool = False) -> str:
 def yardstick_path() -> str:
     """bench.py's measurement helper (isolated rates of the path's instruction sequences); not a product library."""
     return os.path.join(CSRC, "libwf_yardstick.so")
+
+
+def field_probe_path() -> str:
+    """The tests' probe of the field primitives as device code (csrc/field_probe.hip); not a product library."""
+    return os.path.join(CSRC, "libwf_field_probe.so")
 
 
 def lib_path() -> str:

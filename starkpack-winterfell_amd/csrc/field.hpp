@@ -33,7 +33,7 @@ struct F64 {
 
     // x * 2^-64 mod p for x < p * 2^64 (math/src/field/f64/mod.rs:651-661 computes the same value)
     static WF_HD uint64_t mont_reduce(uint64_t xl, uint64_t xh) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__) || defined(WF_FIELD_LIMBS_ON_HOST)
         // explicit 32-bit carry chains: 8 VALU (the 64-bit formulation below compiles to ~16 on gfx950)
         const uint32_t l0 = (uint32_t)xl, l1 = (uint32_t)(xl >> 32), h0 = (uint32_t)xh, h1 = (uint32_t)(xh >> 32);
         uint32_t ah, t, bl, rl, u, rh, r2l;
@@ -56,7 +56,7 @@ struct F64 {
 #endif
     }
     static WF_HD T mul(T a, T b) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__) || defined(WF_FIELD_LIMBS_ON_HOST)
         // 32-bit schoolbook: four v_mad_u64_u32 share the partial products (gfx950 has no 64-bit multiplier)
         const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)b, b1 = (uint32_t)(b >> 32);
         const uint64_t p00 = (uint64_t)a0 * b0;
@@ -77,7 +77,7 @@ struct F64 {
         return r + (fix ? 0xFFFFFFFFull : 0ull);
     }
     static WF_HD T sub(T a, T b) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__) || defined(WF_FIELD_LIMBS_ON_HOST)
         // explicit 32-bit borrow chain (5 VALU): r = a - b, then r -= (2^32 - 1) if it borrowed
         const uint32_t al = (uint32_t)a, ah = (uint32_t)(a >> 32), bl = (uint32_t)b, bh = (uint32_t)(b >> 32);
         uint32_t rl, t, rh;
@@ -338,7 +338,7 @@ struct F128 {
     }
 
     static WF_HD T add(T a, T b) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__) || defined(WF_FIELD_LIMBS_ON_HOST)
         return add_limbs(a, b);
 #else
         u128 x = w(a), z = P() - w(b);
@@ -346,7 +346,7 @@ struct F128 {
 #endif
     }
     static WF_HD T sub(T a, T b) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__) || defined(WF_FIELD_LIMBS_ON_HOST)
         return sub_limbs(a, b);
 #else
         u128 x = w(a), y = w(b);
@@ -366,7 +366,7 @@ struct F128 {
     }
     // (a * b) mod p : 256-bit schoolbook product folded twice with 2^128 = C (mod p)
     static WF_HD T mul(T a, T b) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__) || defined(WF_FIELD_LIMBS_ON_HOST)
         return mul_limbs(a, b);
 #else
         return mul_wide(a, b);

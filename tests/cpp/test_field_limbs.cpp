@@ -106,11 +106,24 @@ int main(int argc, char **argv) {
                                  0xFFF0000000000001ull % F64::P, 0x8000000000000000ull, 0x7FFFFFFFFFFFFFFFull,
                                  0x0000FFFFFFFFFFFFull, 0x0000FFFF0000FFFFull, 0xFFFF0000FFFFFFFFull % F64::P, 0x00000000FFFF0000ull,
                                  0x0FFFFFFFFFFFFFFFull, 0xFFFFFFFFull << 4, 0xFFFFFFFFull << 16, 0xFFFFFFFFull << 28};
+        // the 32-bit limb alphabet of tests/cpp/test_field_edges.cpp: the 43 values below p whose halves are 0, 1, 2, all ones, the
+        // sign bit or a neighbour (with -DWF_FIELD_LIMBS_ON_HOST the subtraction that ends most of these forms is the device's chain)
+        uint64_t alphabet[43];
+        {
+            const uint32_t A[7] = {0, 1, 2, 0x7FFFFFFFu, 0x80000000u, 0xFFFFFFFEu, 0xFFFFFFFFu};
+            int k = 0;
+            for (uint32_t hi : A)
+                for (uint32_t lo : A)
+                    if ((((uint64_t)hi << 32) | lo) < F64::P) alphabet[k++ % 43] = ((uint64_t)hi << 32) | lo;
+            if (k != 43) bad++;
+        }
         for (uint64_t e : edge) chk(e % F64::P);
+        for (uint64_t e : alphabet) chk(e);
         for (long it = 0; it < iters; it++) chk(rnd() % F64::P);
         // every exponent of the order-192 group (the wave-uniform twiddles w_64^(j k) = 2^(3 j k), w_32^k = 2^(6 k), w_8^k = 2^(24 k)
         // and their inverses are among them)
         for (uint64_t e : edge) bad += chk_pow2_192<0>(e % F64::P);
+        for (uint64_t e : alphabet) bad += chk_pow2_192<0>(e);
         for (long it = 0; it < iters / 100 + 1000; it++) bad += chk_pow2_192<0>(rnd() % F64::P);
     }
     printf("checked %ld triples, bad=%ld\n", iters, bad);

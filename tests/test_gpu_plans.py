@@ -38,7 +38,7 @@ def _todays(rotating, pick):
 
 
 PARITY_SWITCHES = PARITY_CORE + _todays(PARITY_ROTATING, ROTATE_PICK)
-PARITY_FILES = ["test_gpu_coset_shard.py", "test_gpu_parity.py", "test_gpu_golden.py"]
+PARITY_FILES = ["test_gpu_coset_shard.py", "test_gpu_parity.py", "test_gpu_golden.py", "test_gpu_field_edges.py"]
 RESIDENT_SWITCHES = RESIDENT_CORE + _todays(RESIDENT_ROTATING, 1)
 RESIDENT_FILES = ["test_gpu_queries.py", "test_gpu_deep.py", "test_gpu_pipeline.py", "test_gpu_wide_resident.py"]
 
