@@ -1,7 +1,7 @@
 // Bring-up microbenchmark (not part of the product): the Sha3_256 kernels against a register-only Keccak-f[1600] loop.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I starkpack-winterfell_amd/csrc scripts/keccak_bench.hip -o /tmp/keccak_bench
 // The yardstick chains permutations in registers (one store per lane at the end): what the vector ALU gives this instruction
-// sequence with nothing else in the way.  The tree (the launch sequence of run_merkle_sha3, csrc/path.hip, on 2^23 leaves)
+// sequence with nothing else in the way.  The tree (the launch sequence of run_merkle with the Sha3 plan, csrc/path.hip, on 2^23 leaves)
 // and the row kernel are reported as permutations per second and as a fraction of it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,7 +10,9 @@
 #include <algorithm>
 #include <vector>
 
+#include "keccak_dev.hpp"
 #include "keccak_kernels.hpp"
+#include "merkle_plan.hpp"
 
 using namespace wf;
 
@@ -54,23 +56,18 @@ static float timeit(K launch, int reps) {
     return ms / reps;
 }
 
-static int tree(const void *leaves, uint64_t n_leaves, void *nodes) {  // run_merkle_sha3
+static int tree(const void *leaves, uint64_t n_leaves, void *nodes) {  // run_merkle_plan<k3::Merge, MERKLE_PLAN_SHA3>, csrc/path.hip
     const uint64_t *children = (const uint64_t *)leaves;
-    uint64_t n_children = n_leaves;
+    uint64_t *out = (uint64_t *)nodes, n_children = n_leaves;
     while (n_children > 1) {
+        const MerkleStep s = merkle_next_launch(n_children, MERKLE_PLAN_SHA3, 0, 0);
         const uint64_t n_par = n_children >> 1;
-        const uint32_t grid = (uint32_t)((n_par + 255) / 256);
-        if (n_par >= (1ull << 15)) {
-            hipLaunchKernelGGL(k_sha3_merkle_level, dim3(grid), dim3(256), 0, 0, (const ulonglong2 *)children, (ulonglong2 *)nodes + n_par * 2, n_par);
-            n_children = n_par;
-        } else {
-            uint32_t total = 0;
-            for (uint64_t t = n_children; t > 1; t >>= 1) total++;
-            const uint32_t levels = std::min<uint32_t>(9, total);
-            hipLaunchKernelGGL(k_sha3_merkle_subtree, dim3(grid), dim3(256), 0, 0, children, (uint64_t *)nodes, n_children, levels);
-            n_children >>= levels;
-        }
-        children = (const uint64_t *)nodes + n_children * 4;
+        if (s.kind == MERKLE_LEVEL)
+            hipLaunchKernelGGL(k_merkle_level<k3::Merge>, dim3((uint32_t)s.grid), dim3(s.block), 0, 0, children, out + n_par * 4, n_par);
+        else
+            hipLaunchKernelGGL(k_merkle_subtree<k3::Merge>, dim3((uint32_t)s.grid), dim3(s.block), 0, 0, children, out, n_children, s.levels);
+        n_children = s.n_children;
+        children = out + n_children * 4;
     }
     return 0;
 }
@@ -96,18 +93,18 @@ int main() {
         CHECK(hipMemcpy(leaves, h.data(), n * 32, hipMemcpyHostToDevice));
         ms = timeit([&] { tree(leaves, n, nodes); }, 10);
         const double r = (double)(n - 1) / ms / 1e6;
-        printf("%-52s %8.3f ms  %7.2f Gperm/s  %5.1f %% of the yardstick\n", "Sha3 tree, 2^23 leaves (run_merkle_sha3 sequence)", ms, r, 100.0 * r / yard);
-        ms = timeit([&] { hipLaunchKernelGGL(k_sha3_merkle_level, dim3((uint32_t)(n / 2 / 256)), dim3(256), 0, 0, (const ulonglong2 *)leaves, (ulonglong2 *)nodes + n, n / 2); }, 10);
+        printf("%-52s %8.3f ms  %7.2f Gperm/s  %5.1f %% of the yardstick\n", "Sha3 tree, 2^23 leaves (the product's sequence)", ms, r, 100.0 * r / yard);
+        ms = timeit([&] { hipLaunchKernelGGL(k_merkle_level<k3::Merge>, dim3((uint32_t)(n / 2 / 256)), dim3(256), 0, 0, (const uint64_t *)leaves, (uint64_t *)nodes + 2 * n, n / 2); }, 10);
         const double r1 = (double)(n / 2) / ms / 1e6;
-        printf("%-52s %8.3f ms  %7.2f Gperm/s  %5.1f %% of the yardstick\n", "k_sha3_merkle_level, 2^22 parents", ms, r1, 100.0 * r1 / yard);
+        printf("%-52s %8.3f ms  %7.2f Gperm/s  %5.1f %% of the yardstick\n", "k_merkle_level<k3::Merge>, 2^22 parents", ms, r1, 100.0 * r1 / yard);
         CHECK(hipFree(leaves));
         CHECK(hipFree(nodes));
     }
     // row kernel: permutations per row = floor(row bytes / 136) + 1
     struct Shape { uint32_t log_rows, cols; const char *name; };
-    const Shape shapes[] = {{23, 8, "k_sha3_hash_rows<F64>, 2^23 rows x 8 (64 bytes)"},
-                            {16, 64, "k_sha3_hash_rows<F64>, 2^16 rows x 64 (512 bytes)"},
-                            {20, 64, "k_sha3_hash_rows<F64>, 2^20 rows x 64 (512 bytes)"}};
+    const Shape shapes[] = {{23, 8, "k_hash_rows_sponge<F64, k3::Absorb>, 2^23 rows x 8 (64 bytes)"},
+                            {16, 64, "k_hash_rows_sponge<F64, k3::Absorb>, 2^16 rows x 64 (512 bytes)"},
+                            {20, 64, "k_hash_rows_sponge<F64, k3::Absorb>, 2^20 rows x 64 (512 bytes)"}};
     for (const Shape &sh : shapes) {
         const uint64_t rows = 1ull << sh.log_rows;
         uint64_t *lde;
@@ -124,7 +121,7 @@ int main() {
         a.n_traces = 1;
         a.leaves = leaves;
         a.digest_words = 8;
-        ms = timeit([&] { hipLaunchKernelGGL(k_sha3_hash_rows<F64>, dim3((uint32_t)(rows / 256)), dim3(256), 0, 0, a); }, 10);
+        ms = timeit([&] { hipLaunchKernelGGL((k_hash_rows_sponge<F64, k3::Absorb>), dim3((uint32_t)(rows / 256)), dim3(256), 0, 0, a); }, 10);
         const double perms = (double)rows * (sh.cols * 8 / 136 + 1), r = perms / ms / 1e6;
         printf("%-52s %8.3f ms  %7.2f Gperm/s  %5.1f %% of the yardstick  (%.0f GB/s read)\n", sh.name, ms, r, 100.0 * r / yard,
                (double)rows * sh.cols * 8 / ms / 1e6);

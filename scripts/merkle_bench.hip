@@ -208,7 +208,7 @@ int main() {
     };
     for (uint32_t blocks : {1024u, 2048u, 4096u, 8192u}) {
         char nm[96];
-        float ms = timeit([&] { hipLaunchKernelGGL(k_merkle_level2, dim3(blocks), dim3(256), 0, 0, leaves, nodes + n_par * 8, nodes + n_grand * 8, n_grand); }, 10);
+        float ms = timeit([&] { hipLaunchKernelGGL(k_merkle_level2<b3::Merge<8>>, dim3(blocks), dim3(256), 0, 0, leaves, nodes + n_par * 8, nodes + n_grand * 8, n_grand); }, 10);
         snprintf(nm, sizeof nm, "product k_merkle_level2, %u blocks", blocks);
         report(nm, ms);
         ms = timeit([&] { hipLaunchKernelGGL(k_l2_upfront<true>, dim3(blocks), dim3(256), 0, 0, leaves, nodes2 + n_par * 8, nodes2 + n_grand * 8, n_grand); }, 10);
@@ -229,15 +229,15 @@ int main() {
         printf("three levels per launch, %u blocks             %7.3f ms  %6.2f Gcompress/s (7 per lane)\n", blocks, ms, 7.0 * n3 / ms / 1e6);
         // reference: two launches of the product kernel covering the same three levels
         float ms2 = timeit([&] {
-            hipLaunchKernelGGL(k_merkle_level2, dim3(2048), dim3(256), 0, 0, leaves, nodes + n_par * 8, nodes + n_grand * 8, n_grand);
-            hipLaunchKernelGGL(k_merkle_level, dim3((uint32_t)(n3 / 256)), dim3(256), 0, 0, nodes + n_grand * 8, nodes + n3 * 8, n3); }, 10);
+            hipLaunchKernelGGL(k_merkle_level2<b3::Merge<8>>, dim3(2048), dim3(256), 0, 0, leaves, nodes + n_par * 8, nodes + n_grand * 8, n_grand);
+            hipLaunchKernelGGL(k_merkle_level<b3::Merge<8>>, dim3((uint32_t)(n3 / 256)), dim3(256), 0, 0, nodes + n_grand * 8, nodes + n3 * 8, n3); }, 10);
         printf("   product: level2 + level for the same levels  %7.3f ms\n", ms2);
     }
     {
         float ms = timeit([&] { hipLaunchKernelGGL(k_l2_upfront<false>, dim3((uint32_t)(n_grand / 256)), dim3(256), 0, 0, leaves, nodes2 + n_par * 8, nodes2 + n_grand * 8, n_grand); }, 10);
         report("loads up front, one item per thread", ms);
         check("one item per thread");
-        ms = timeit([&] { hipLaunchKernelGGL(k_merkle_level, dim3((uint32_t)(n_par / 256)), dim3(256), 0, 0, leaves, nodes2 + n_par * 8, n_par); }, 10);
+        ms = timeit([&] { hipLaunchKernelGGL(k_merkle_level<b3::Merge<8>>, dim3((uint32_t)(n_par / 256)), dim3(256), 0, 0, leaves, nodes2 + n_par * 8, n_par); }, 10);
         printf("%-44s %7.3f ms  %6.2f Gcompress/s\n", "k_merkle_level (one level, 2^22 parents)", ms, n_par / ms / 1e6);
     }
     return 0;

@@ -4,7 +4,7 @@
 // lane at the end -- what the vector ALU gives the instruction sequence with nothing else in the way.
 //   form 1  rp::permute       one lane per permutation
 //   form 2  rp::permute_lane  one state element per lane, 16 lanes per permutation
-// Then: one tree level of 2^8 .. 2^18 parents in either form (the switch of run_merkle_rp64, csrc/path.hip, is read off this
+// Then: one tree level of 2^8 .. 2^18 parents in either form (MERKLE_PLAN_RP64.level_min_log, csrc/merkle_plan.hpp, is read off this
 // table), the tree over 2^23 leaves, and the row kernel, each as permutations per second and as a fraction of form 1's loop.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "keccak_kernels.hpp"
 #include "rescue_kernels.hpp"
 
 using namespace wf;
@@ -64,8 +65,8 @@ static float timeit(K launch, int reps) {
 }
 
 static void level_form1(const void *children, void *nodes, uint64_t n_par) {
-    hipLaunchKernelGGL(k_rp64_merkle_level, dim3((uint32_t)((n_par + 255) / 256)), dim3(256), 0, 0, (const ulonglong2 *)children,
-                       (ulonglong2 *)nodes + n_par * 2, n_par);
+    hipLaunchKernelGGL(k_merkle_level<rp::Merge>, dim3((uint32_t)((n_par + 255) / 256)), dim3(256), 0, 0, (const uint64_t *)children,
+                       (uint64_t *)nodes + n_par * 4, n_par);
 }
 
 static void subtree(const void *children, void *nodes, uint64_t n_children, uint32_t levels) {
@@ -74,7 +75,7 @@ static void subtree(const void *children, void *nodes, uint64_t n_children, uint
                        dim3(RP64_SUBTREE_THREADS), 0, 0, (const uint64_t *)children, (uint64_t *)nodes, n_children, levels);
 }
 
-static void tree(const void *leaves, uint64_t n_leaves, void *nodes, uint32_t level_min_log) {  // run_merkle_rp64
+static void tree(const void *leaves, uint64_t n_leaves, void *nodes, uint32_t level_min_log) {  // the Rp64 plan of run_merkle with the switch at 2^level_min_log
     const uint64_t *children = (const uint64_t *)leaves;
     uint64_t n_children = n_leaves;
     while (n_children > 1) {
@@ -85,7 +86,7 @@ static void tree(const void *leaves, uint64_t n_leaves, void *nodes, uint32_t le
         } else {
             uint32_t total = 0;
             for (uint64_t t = n_children; t > 1; t >>= 1) total++;
-            const uint32_t levels = std::min<uint32_t>(RP64_SUBTREE_LEVELS, total);
+            const uint32_t levels = std::min<uint32_t>(MERKLE_PLAN_RP64.subtree_levels, total);
             subtree(children, nodes, n_children, levels);
             n_children >>= levels;
         }
@@ -124,7 +125,7 @@ int main(int argc, char **argv) {
         CHECK(hipMemcpy(leaves, h.data(), n * 32, hipMemcpyHostToDevice));
     }
     if (!quick) {
-        printf("one tree level, milliseconds (form 1 = k_rp64_merkle_level, form 2 = k_rp64_merkle_subtree with one level)\n");
+        printf("one tree level, milliseconds (form 1 = k_merkle_level<rp::Merge>, form 2 = k_rp64_merkle_subtree with one level)\n");
         for (uint32_t lg = 8; lg <= 18; lg++) {
             const uint64_t n_par = 1ull << lg;
             const float m1 = timeit([&] { level_form1(leaves, nodes, n_par); }, 3);
@@ -139,16 +140,16 @@ int main(int argc, char **argv) {
     {
         ms = timeit([&] { tree(leaves, n, nodes, 16); }, 2);
         const double r = (double)(n - 1) / ms / 1e3;
-        printf("%-56s %9.3f ms  %8.2f Mperm/s  %5.1f %% of the yardstick\n", "tree, 2^23 leaves (run_merkle_rp64 sequence)", ms, r, 100.0 * r / yard);
+        printf("%-56s %9.3f ms  %8.2f Mperm/s  %5.1f %% of the yardstick\n", "tree, 2^23 leaves (the product's sequence)", ms, r, 100.0 * r / yard);
         ms = timeit([&] { level_form1(leaves, nodes, n / 2); }, 2);
         const double r1 = (double)(n / 2) / ms / 1e3;
-        printf("%-56s %9.3f ms  %8.2f Mperm/s  %5.1f %% of the yardstick\n", "k_rp64_merkle_level, 2^22 parents", ms, r1, 100.0 * r1 / yard);
+        printf("%-56s %9.3f ms  %8.2f Mperm/s  %5.1f %% of the yardstick\n", "k_merkle_level<rp::Merge>, 2^22 parents", ms, r1, 100.0 * r1 / yard);
     }
     CHECK(hipFree(leaves));
     CHECK(hipFree(nodes));
     // row kernel: permutations per row = ceil(elements / 8)
     struct Shape { uint32_t log_rows, cols; const char *name; };
-    const Shape shapes[] = {{23, 8, "k_rp64_hash_rows, 2^23 rows x 8"}, {20, 64, "k_rp64_hash_rows, 2^20 rows x 64"}};
+    const Shape shapes[] = {{23, 8, "k_hash_rows_sponge<F64, rp::Absorb>, 2^23 rows x 8"}, {20, 64, "k_hash_rows_sponge<F64, rp::Absorb>, 2^20 rows x 64"}};
     for (const Shape &sh : shapes) {
         const uint64_t rows = 1ull << sh.log_rows;
         uint64_t *lde;
@@ -165,7 +166,7 @@ int main(int argc, char **argv) {
         a.n_traces = 1;
         a.leaves = lv;
         a.digest_words = 8;
-        ms = timeit([&] { hipLaunchKernelGGL(k_rp64_hash_rows, dim3((uint32_t)(rows / 256)), dim3(256), 0, 0, a); }, 2);
+        ms = timeit([&] { hipLaunchKernelGGL((k_hash_rows_sponge<F64, rp::Absorb>), dim3((uint32_t)(rows / 256)), dim3(256), 0, 0, a); }, 2);
         const double perms = (double)rows * ((sh.cols + 7) / 8), r = perms / ms / 1e3;
         printf("%-56s %9.3f ms  %8.2f Mperm/s  %5.1f %% of the yardstick\n", sh.name, ms, r, 100.0 * r / yard);
         CHECK(hipFree(lde));

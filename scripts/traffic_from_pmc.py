@@ -37,8 +37,14 @@ LOGICAL = [
     ("evaluate", ["k_seg_strided<wf::F64, 1,", "k_seg_last<wf::F64, 1,", "k_seg_last_hash<wf::F64,", "k_seg_strided<wf::F128, 1,",
                   "k_seg_last<wf::F128, 1,", "k_seg_last_hash<wf::F128,", "k_seg_strided_wide<wf::F64, 1,",
                   "k_seg_last_hash_tp<wf::F64,", "k_seg_last_hash_tp<wf::F128,"]),
-    ("hash_rows", ["k_hash_rows", "k_hash_chunks", "k_hash_merge_chunks"]),  # (k_hash_chunks also matches k_hash_chunks_staged)
-    ("merkle", ["k_merkle_level", "k_merkle_subtree"])  # k_merkle_level also matches k_merkle_level2,
+    # (k_hash_chunks also matches k_hash_chunks_staged; k_hash_rows also matches k_hash_rows_sponge<F, A>, the leaf kernel of
+    # Sha3_256 and Rp64_256 -- on purpose: a profile of such a commitment has its leaf hashing in this group)
+    ("hash_rows", ["k_hash_rows", "k_hash_chunks", "k_hash_merge_chunks"]),
+    # k_merkle_level also matches k_merkle_level2.  The tree kernels are templates on the hasher's merge policy
+    # (k_merkle_level<wf::b3::Merge<8>>, <wf::k3::Merge>, <wf::rp::Merge>): the substrings take every hasher's, and
+    # k_rp64_merkle_subtree (the lane-form top of the Rp64_256 tree) is listed so that the Sha3_256 and Rp64_256 trees fall
+    # into this group whole, deliberately.  cfg 2 (BLAKE3) launches k_merkle_level2 x3 and k_merkle_subtree x2 as before.
+    ("merkle", ["k_merkle_level", "k_merkle_subtree", "k_rp64_merkle_subtree"])
 ]
 # Round 4 calibration: the SECOND strided evaluation pass of cfg 3 must read the 17.18 GB intermediate exactly once (nothing can
 # absorb 16 GiB); its raw counter is 8.59 GB -- with 64-byte tile rows (round 3's kernel, same raw figure) as with 128-byte rows.

@@ -167,6 +167,19 @@ __device__ __forceinline__ void merge_quad(const uint32_t *msg, uint32_t q, uint
     out_hi = (DW == 6 && q >= 2) ? 0u : (b ^ d);  // (words 6, 7 of a 24-byte digest's slot are zero)
 }
 
+// What the tree kernels of kernels.hpp need of a hasher: digests in 32-byte slots of NW words of type W, merge() on two
+// child slots, and whether the narrow levels have a several-lanes-per-node form (merge_quad).
+template <int DW>
+struct Merge {
+    using W = uint32_t;
+    static constexpr int NW = 8;
+    static constexpr bool HAS_QUAD = true;
+    static __device__ __forceinline__ void merge(const W (&in)[2 * NW], W (&out)[NW]) { merge_slots<DW>(in, out); }
+    static __device__ __forceinline__ void merge_quad(const W *msg, uint32_t q, W &out_lo, W &out_hi) {
+        b3::merge_quad<DW>(msg, q, out_lo, out_hi);
+    }
+};
+
 // Hash of a message of `len` <= 1024 bytes (one chunk; len a multiple of 4) delivered block by block:
 // load(block_index, m) must fill the 16 words of 64-byte block `block_index`, zero-padded past `len`.
 // Longer messages go through chunk_cv + merge_chunk_cvs below (one lane per chunk).

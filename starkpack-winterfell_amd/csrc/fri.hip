@@ -35,10 +35,10 @@ static int fri_layer_commit_dev(wf_ctx *ctx, hipStream_t st, uint32_t ext, const
                        (T *)d_transposed, rows, folding, ext);
     HIP_TRY(hipGetLastError());
     prof_mark(ctx, st, "fri.hash_values");
-    int rc = path_hash_rows(ctx, st, F::FIELD_ID == 1 ? WF_FIELD_F64 : WF_FIELD_F128, d_transposed, 0, rows, folding * ext, folding * ext, 1, d_leaves, ctx->digest_bytes, ctx->hasher);
+    int rc = path_hash_rows(ctx, st, F::FIELD_ID == 1 ? WF_FIELD_F64 : WF_FIELD_F128, d_transposed, 0, rows, folding * ext, folding * ext, 1, d_leaves, ctx->hasher, ctx->digest_bytes);
     if (rc) return rc;
     prof_mark(ctx, st, "fri.merkle");
-    rc = path_merkle(ctx, st, d_leaves, rows, d_nodes, ctx->digest_bytes, ctx->hasher);
+    rc = path_merkle(ctx, st, d_leaves, rows, d_nodes, ctx->hasher, ctx->digest_bytes);
     prof_mark(ctx, st, "between_calls");
     return rc;
 }

@@ -135,6 +135,20 @@ WF_HD void sha3_256_lanes(uint64_t n_lanes, Next &&next, uint64_t (&out)[4]) {
     for (int i = 0; i < 4; i++) out[i] = s[i];
 }
 
+// The hasher as the tree kernels (Merge) and the lane-per-row leaf kernel (Absorb) of the *_kernels.hpp headers take it:
+// digests are four 64-bit words; the message lanes are the canonical values of the elements.
+struct Merge {
+    using W = uint64_t;
+    static constexpr int NW = 4;
+    static constexpr bool HAS_QUAD = false;
+    static WF_HD void merge(const W (&in)[2 * NW], W (&out)[NW]) { sha3_merge(in, out); }
+};
+struct Absorb {
+    static constexpr bool CANONICAL = true;
+    template <class Next>
+    static WF_HD void absorb(uint64_t n_lanes, Next &&next, uint64_t (&out)[4]) { sha3_256_lanes(n_lanes, next, out); }
+};
+
 // Any byte length (host test only: the library itself never hashes a partial lane).
 static inline void sha3_256_bytes(const unsigned char *msg, size_t len, unsigned char digest[32]) {
     uint64_t s[25] = {0};

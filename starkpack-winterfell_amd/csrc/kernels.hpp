@@ -62,6 +62,33 @@ __device__ __forceinline__ uint4 digest_hi(uint32_t w4, uint32_t w5, uint32_t w6
     return digest_words == 6 ? make_uint4(w4, w5, 0u, 0u) : make_uint4(w4, w5, w6, w7);
 }
 
+// Digest slots as 16-byte accesses, for 32-bit (BLAKE3) and 64-bit (Sha3, Rp64) digest words: load_slots reads a child
+// pair (64 contiguous bytes), store_digest writes one 32-byte slot.  p must be 16-byte aligned.
+__device__ __forceinline__ void load_slots(const uint32_t *p, uint32_t (&m)[16]) {
+    const uint4 *src = reinterpret_cast<const uint4 *>(p);
+    const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
+    m[0] = q0.x; m[1] = q0.y; m[2] = q0.z; m[3] = q0.w;
+    m[4] = q1.x; m[5] = q1.y; m[6] = q1.z; m[7] = q1.w;
+    m[8] = q2.x; m[9] = q2.y; m[10] = q2.z; m[11] = q2.w;
+    m[12] = q3.x; m[13] = q3.y; m[14] = q3.z; m[15] = q3.w;
+}
+__device__ __forceinline__ void load_slots(const uint64_t *p, uint64_t (&in)[8]) {
+    const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(p);
+    const ulonglong2 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
+    in[0] = q0.x; in[1] = q0.y; in[2] = q1.x; in[3] = q1.y;
+    in[4] = q2.x; in[5] = q2.y; in[6] = q3.x; in[7] = q3.y;
+}
+__device__ __forceinline__ void store_digest(uint32_t *p, const uint32_t (&cv)[8]) {
+    uint4 *dst = reinterpret_cast<uint4 *>(p);
+    dst[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
+    dst[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+}
+__device__ __forceinline__ void store_digest(uint64_t *p, const uint64_t (&d)[4]) {
+    ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(p);
+    dst[0] = make_ulonglong2(d[0], d[1]);
+    dst[1] = make_ulonglong2(d[2], d[3]);
+}
+
 template <class F>
 __device__ __forceinline__ void elem_words(typename F::T v, uint32_t *w);
 template <>
@@ -428,97 +455,86 @@ static __global__ void __launch_bounds__(256) k_hash_merge_chunks_par(const uint
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Merkle levels (build_merkle_nodes, crypto/src/merkle/mod.rs:350-374): each work-group folds 2*blockDim children
-// through up to `levels` levels, keeping the intermediate digests in LDS and writing every level to `nodes`.
-// children: digests of the level below (n_children of them); the parents level has n_children/2 nodes stored at
+// Merkle levels (build_merkle_nodes, crypto/src/merkle/mod.rs:350-374), for every hasher: M is its merge policy
+// (b3::Merge<DW>, k3::Merge, rp::Merge), digests are M::NW words of type M::W in 32-byte slots.  Each work-group folds
+// 2*blockDim children through up to `levels` levels, keeping the intermediate digests in LDS and writing every level to
+// `nodes`.  children: digests of the level below (n_children of them); the parents level has n_children/2 nodes stored at
 // nodes[n_children/2 .. n_children).
-template <int DW>
-__global__ void __launch_bounds__(256) k_merkle_subtree(const uint32_t *__restrict__ children,
-                                                        uint32_t *__restrict__ nodes, uint64_t n_children,
+template <class M>
+__global__ void __launch_bounds__(256) k_merkle_subtree(const typename M::W *__restrict__ children,
+                                                        typename M::W *__restrict__ nodes, uint64_t n_children,
                                                         uint32_t levels) {
-    __shared__ uint32_t sh[256 * 8];
+    using W = typename M::W;
+    constexpr int NW = M::NW;
+    __shared__ W sh[256 * NW];
     const uint32_t tid = threadIdx.x;
     uint64_t n_par = n_children >> 1;                        // nodes in the first produced level
     uint64_t first = (uint64_t)blockIdx.x * blockDim.x;      // this group's slice of that level
     uint32_t width = (uint32_t)min((uint64_t)blockDim.x, n_par - first);
-    uint32_t m[16], cv[8];
+    W in[2 * NW], d[NW];
     if (tid < width) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(children + (first + tid) * 16);
-        uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-        m[0] = q0.x; m[1] = q0.y; m[2] = q0.z; m[3] = q0.w;
-        m[4] = q1.x; m[5] = q1.y; m[6] = q1.z; m[7] = q1.w;
-        m[8] = q2.x; m[9] = q2.y; m[10] = q2.z; m[11] = q2.w;
-        m[12] = q3.x; m[13] = q3.y; m[14] = q3.z; m[15] = q3.w;
-        b3::merge_slots<DW>(m, cv);
-        uint4 *dst = reinterpret_cast<uint4 *>(nodes + (n_par + first + tid) * 8);
-        dst[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
-        dst[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+        load_slots(children + (first + tid) * 2 * NW, in);
+        M::merge(in, d);
+        store_digest(nodes + (n_par + first + tid) * NW, d);
 #pragma unroll
-        for (int i = 0; i < 8; i++) sh[tid * 8 + i] = cv[i];
+        for (int i = 0; i < NW; i++) sh[tid * NW + i] = d[i];
     }
     for (uint32_t lv = 1; lv < levels; lv++) {
         __syncthreads();
         n_par >>= 1;
         first >>= 1;
         width >>= 1;
-        if (width <= 64) {
-            // narrow levels: four lanes per node (b3::merge_quad) -- a level is one compression's latency, and a lane of a
-            // quad issues a third of the instructions (a 9-level launch 14 -> 9 us)
-            const uint32_t node = tid >> 2, q = tid & 3;
-            const bool act = node < width;  // whole quads
-            uint32_t lo = 0, hi = 0;
-            if (act) b3::merge_quad<DW>(sh + node * 16, q, lo, hi);
-            __syncthreads();
-            if (act) {
-                uint32_t *dst = nodes + (n_par + first + node) * 8;
-                dst[q] = lo;
-                dst[4 + q] = hi;
-                sh[node * 8 + q] = lo;
-                sh[node * 8 + 4 + q] = hi;
+        if constexpr (M::HAS_QUAD) {
+            if (width <= 64) {
+                // narrow levels: four lanes per node (b3::merge_quad) -- a level is one compression's latency, and a lane of
+                // a quad issues a third of the instructions (a 9-level launch 14 -> 9 us)
+                const uint32_t node = tid >> 2, q = tid & 3;
+                const bool act = node < width;  // whole quads
+                W lo = 0, hi = 0;
+                if (act) M::merge_quad(sh + node * 2 * NW, q, lo, hi);
+                __syncthreads();
+                if (act) {
+                    W *dst = nodes + (n_par + first + node) * NW;
+                    dst[q] = lo;
+                    dst[4 + q] = hi;
+                    sh[node * NW + q] = lo;
+                    sh[node * NW + 4 + q] = hi;
+                }
+                continue;
             }
-            continue;
         }
         const bool act = tid < width;
         if (act) {
 #pragma unroll
-            for (int i = 0; i < 16; i++) m[i] = sh[tid * 16 + i];
-            b3::merge_slots<DW>(m, cv);
+            for (int i = 0; i < 2 * NW; i++) in[i] = sh[tid * 2 * NW + i];
+            M::merge(in, d);
         }
         __syncthreads();
         if (act) {
-            uint4 *dst = reinterpret_cast<uint4 *>(nodes + (n_par + first + tid) * 8);
-            dst[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
-            dst[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+            store_digest(nodes + (n_par + first + tid) * NW, d);
 #pragma unroll
-            for (int i = 0; i < 8; i++) sh[tid * 8 + i] = cv[i];
+            for (int i = 0; i < NW; i++) sh[tid * NW + i] = d[i];
         }
     }
     // the launch that produces the root also writes nodes[0] = Digest::default() (merkle/mod.rs:355) -- by a kernel rather
     // than a memset so that a captured graph of the commitment replays it
     if (blockIdx.x == 0 && tid == 0 && (n_children >> levels) == 1) {
-        uint4 *dst = reinterpret_cast<uint4 *>(nodes);
-        dst[0] = make_uint4(0, 0, 0, 0);
-        dst[1] = make_uint4(0, 0, 0, 0);
+        const W zero[NW] = {};
+        store_digest(nodes, zero);
     }
 }
 
-// One Merkle level per launch (used while a level still fills the chip): parents[i] = merge(children[2i], children[2i+1]).
-template <int DW>
-__global__ void __launch_bounds__(256) k_merkle_level(const uint32_t *__restrict__ children,
-                                                      uint32_t *__restrict__ parents, uint64_t n_parents) {
+// One Merkle level per launch (used while a level still fills the chip): parents[i] = merge(children[2i], children[2i+1]);
+// one lane per parent, 64 contiguous bytes in, 32 out.
+template <class M>
+__global__ void __launch_bounds__(256) k_merkle_level(const typename M::W *__restrict__ children,
+                                                      typename M::W *__restrict__ parents, uint64_t n_parents) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_parents) return;
-    const uint4 *src = reinterpret_cast<const uint4 *>(children + i * 16);
-    uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-    uint32_t m[16], cv[8];
-    m[0] = q0.x; m[1] = q0.y; m[2] = q0.z; m[3] = q0.w;
-    m[4] = q1.x; m[5] = q1.y; m[6] = q1.z; m[7] = q1.w;
-    m[8] = q2.x; m[9] = q2.y; m[10] = q2.z; m[11] = q2.w;
-    m[12] = q3.x; m[13] = q3.y; m[14] = q3.z; m[15] = q3.w;
-    b3::merge_slots<DW>(m, cv);
-    uint4 *dst = reinterpret_cast<uint4 *>(parents + i * 8);
-    dst[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
-    dst[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+    typename M::W in[2 * M::NW], d[M::NW];
+    load_slots(children + i * 2 * M::NW, in);
+    M::merge(in, d);
+    store_digest(parents + i * M::NW, d);
 }
 
 // 24-byte digests travel between host arrays (ByteDigest<24>, 24 bytes apart: the reference's Vec<Digest>) and the device's
@@ -562,32 +578,25 @@ static __global__ void __launch_bounds__(256) k_gather_digests(const uint4 *__re
 // Two Merkle levels per launch: lane i reads four children (128 contiguous bytes), writes parents 2i, 2i+1 and
 // grandparent i.  Halves the launches and the re-reads of the level-per-launch form for the wide levels.
 // (six waves per SIMD instead of the seven its 72 VGPRs allow: 0.251 -> 0.240 ms for the 2^23-leaf tree, same box, same code)
-template <int DW>
+template <class M>
 __attribute__((amdgpu_waves_per_eu(6, 6)))
-__global__ void __launch_bounds__(256) k_merkle_level2(const uint32_t *__restrict__ children,
-                                                       uint32_t *__restrict__ parents,
-                                                       uint32_t *__restrict__ grandparents, uint64_t n_grand) {
+__global__ void __launch_bounds__(256) k_merkle_level2(const typename M::W *__restrict__ children,
+                                                       typename M::W *__restrict__ parents,
+                                                       typename M::W *__restrict__ grandparents, uint64_t n_grand) {
+    constexpr int NW = M::NW;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_grand; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint4 *src = reinterpret_cast<const uint4 *>(children + i * 32);
-    uint32_t m[16], cv[8], g[16];
+        const typename M::W *src = children + i * 4 * NW;  // four children: 128 contiguous bytes
+        typename M::W in[2 * NW], d[NW], g[2 * NW];
 #pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const uint4 q0 = src[4 * h], q1 = src[4 * h + 1], q2 = src[4 * h + 2], q3 = src[4 * h + 3];
-        m[0] = q0.x; m[1] = q0.y; m[2] = q0.z; m[3] = q0.w;
-        m[4] = q1.x; m[5] = q1.y; m[6] = q1.z; m[7] = q1.w;
-        m[8] = q2.x; m[9] = q2.y; m[10] = q2.z; m[11] = q2.w;
-        m[12] = q3.x; m[13] = q3.y; m[14] = q3.z; m[15] = q3.w;
-        b3::merge_slots<DW>(m, cv);
-        uint4 *dst = reinterpret_cast<uint4 *>(parents + (2 * i + h) * 8);
-        dst[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
-        dst[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+        for (int h = 0; h < 2; h++) {
+            load_slots(src + h * 2 * NW, in);
+            M::merge(in, d);
+            store_digest(parents + (2 * i + h) * NW, d);
 #pragma unroll
-        for (int k = 0; k < 8; k++) g[8 * h + k] = cv[k];
-    }
-    b3::merge_slots<DW>(g, cv);
-    uint4 *dst = reinterpret_cast<uint4 *>(grandparents + i * 8);
-    dst[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
-    dst[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+            for (int k = 0; k < NW; k++) g[NW * h + k] = d[k];
+        }
+        M::merge(g, d);
+        store_digest(grandparents + i * NW, d);
     }
 }
 

@@ -4,7 +4,9 @@
 #include "wf_internal.hpp"
 
 #include "kernels.hpp"
+#include "keccak_dev.hpp"
 #include "keccak_kernels.hpp"
+#include "merkle_plan.hpp"
 #include "rescue_kernels.hpp"
 #include "seg_kernels.hpp"
 #include "col_kernels.hpp"
@@ -680,9 +682,12 @@ static void launch_merge_chunks(hipStream_t st, const void *cvs, uint32_t n_chun
                            n_chunks, n_rows, (uint32_t *)leaves, dw);
 }
 
+// (hasher, digest_bytes): enum wf_hasher and the digest size in bytes -- 32, or 24 for Blake3_192 (48-byte merge inputs; the
+// slots' last two words are zeros)
 template <class F>
 static int run_hash_rows(wf_ctx *ctx, hipStream_t st, const void *lde, uint64_t trace_elems, uint64_t n_rows, uint32_t row_width,
-                         uint32_t epr, uint32_t n_traces, void *leaves, uint32_t dw = 8, uint32_t hasher = WF_HASH_BLAKE3) {
+                         uint32_t epr, uint32_t n_traces, void *leaves, uint32_t hasher, uint32_t digest_bytes) {
+    const uint32_t dw = digest_bytes / 4;
     HashArgs<F> h;
     h.lde = (const typename F::T *)lde;
     h.trace_elems = trace_elems;
@@ -694,21 +699,15 @@ static int run_hash_rows(wf_ctx *ctx, hipStream_t st, const void *lde, uint64_t 
     h.digest_words = dw;
     const uint32_t threads = 256;
     const uint64_t grid = (n_rows + threads - 1) / threads;
-    if (hasher == WF_HASH_SHA3_256) {  // one lane per row absorbs the whole row, whatever its length
+    if (hasher != WF_HASH_BLAKE3) {  // the sponge hashers: one lane per row absorbs the whole row, whatever its length
+        if (hasher == WF_HASH_RP64_256 && F::FIELD_ID != 1) return fail(WF_ERR_FIELD, "Rp64_256 hashes elements of the f64 field only");
         if (grid > 0x7FFFFFFFull) return fail(WF_ERR_ARG, "too many rows for one launch");
-        hipLaunchKernelGGL(k_sha3_hash_rows<F>, dim3((uint32_t)grid), dim3(threads), 0, st, h);
+        if (hasher == WF_HASH_SHA3_256)
+            hipLaunchKernelGGL((k_hash_rows_sponge<F, k3::Absorb>), dim3((uint32_t)grid), dim3(threads), 0, st, h);
+        else if constexpr (F::FIELD_ID == 1)  // (the sponge takes the stored (Montgomery) elements as they are)
+            hipLaunchKernelGGL((k_hash_rows_sponge<F, rp::Absorb>), dim3((uint32_t)grid), dim3(threads), 0, st, h);
         HIP_TRY(hipGetLastError());
         return 0;
-    }
-    if (hasher == WF_HASH_RP64_256) {  // likewise one lane per row; the sponge takes the stored (Montgomery) elements as they are
-        if constexpr (F::FIELD_ID == 1) {
-            if (grid > 0x7FFFFFFFull) return fail(WF_ERR_ARG, "too many rows for one launch");
-            hipLaunchKernelGGL(k_rp64_hash_rows, dim3((uint32_t)grid), dim3(threads), 0, st, h);
-            HIP_TRY(hipGetLastError());
-            return 0;
-        } else {
-            return fail(WF_ERR_FIELD, "Rp64_256 hashes elements of the f64 field only");
-        }
     }
     const uint64_t row_bytes = (uint64_t)n_traces * epr * F::BYTES;
     if (row_bytes <= 1024) {  // single BLAKE3 chunk: one lane per row, no subtree stack
@@ -743,114 +742,46 @@ static int run_hash_rows(wf_ctx *ctx, hipStream_t st, const void *lde, uint64_t 
     return 0;
 }
 
-template <int DW>
-static int run_merkle_dw(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes) {
-    // (nodes[0] = Digest::default(), merkle/mod.rs:355, is written by the launch that produces the root)
-    const uint32_t *children = (const uint32_t *)leaves;
+// The tree of every hasher: the launches merkle_next_launch (merkle_plan.hpp) names for the hasher's plan, each level
+// written to nodes[n .. 2n).  M: the hasher's merge policy (only a plan with two-level launches instantiates
+// k_merkle_level2<M>).  A pure kernel sequence.
+// (nodes[0] = Digest::default(), merkle/mod.rs:355, is written by the launch that produces the root)
+template <class M, const MerklePlan &PLAN>
+static int run_merkle_plan(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes) {
+    typedef typename M::W W;
+    const W *children = (const W *)leaves;
+    W *const out = (W *)nodes;
     uint64_t n_children = n_leaves;
     while (n_children > 1) {
+        const MerkleStep s = merkle_next_launch(n_children, PLAN, ctx->tune.merkle_l2_min, (uint32_t)ctx->num_cus);
+        // (for every plan; BLAKE3 cannot get there: its two-level grid is capped, its other kernels see levels below 2^30 parents)
+        if (s.grid > 0x7FFFFFFFull) return fail(WF_ERR_ARG, "too many leaves for one launch");
+        const dim3 grid((uint32_t)s.grid), block(s.block);
         const uint64_t n_par = n_children >> 1;
-        const uint32_t threads = 256;
-        const uint64_t grid = (n_par + threads - 1) / threads;
-        // levels of >= 2^18 parents: two per launch; below that the LDS subtree kernel folds 9 levels per launch (one
-        // launch less than switching at 2^16, 5 us at 2^23 leaves).  WF_EXP_MERKLE_L2_MIN: tuning switch
-        const uint32_t l2_min = ctx->tune.merkle_l2_min;
-        if (n_par >= ((uint64_t)1 << l2_min)) {  // two levels that still fill the chip: one lane per grandparent
-            const uint64_t n_grand = n_par >> 1;
-            const uint64_t blocks2 = std::min<uint64_t>((n_grand + threads - 1) / threads, (uint64_t)ctx->num_cus * 8);  // grid-stride
-            hipLaunchKernelGGL(k_merkle_level2<DW>, dim3((uint32_t)blocks2), dim3(threads), 0, st,
-                               children, (uint32_t *)nodes + n_par * 8, (uint32_t *)nodes + n_grand * 8, n_grand);
-            HIP_TRY(hipGetLastError());
-            n_children = n_grand;
-        } else if (n_par >= (1u << 15) && l2_min == 16) {  // a level that still fills the chip: one lane per node
-            hipLaunchKernelGGL(k_merkle_level<DW>, dim3((uint32_t)grid), dim3(threads), 0, st, children,
-                               (uint32_t *)nodes + n_par * 8, n_par);
-            HIP_TRY(hipGetLastError());
-            n_children = n_par;
-        } else {                    // the top of the tree: up to 9 levels per launch through LDS
-            uint32_t total_levels = 0;
-            for (uint64_t t = n_children; t > 1; t >>= 1) total_levels++;
-            const uint32_t levels = std::min<uint32_t>(9, total_levels);
-            hipLaunchKernelGGL(k_merkle_subtree<DW>, dim3((uint32_t)grid), dim3(threads), 0, st, children,
-                               (uint32_t *)nodes, n_children, levels);
-            HIP_TRY(hipGetLastError());
-            n_children >>= levels;
+        if (s.kind == MERKLE_LEVEL) {
+            hipLaunchKernelGGL(k_merkle_level<M>, grid, block, 0, st, children, out + n_par * M::NW, n_par);
+        } else if (s.kind == MERKLE_SUBTREE) {
+            if constexpr (std::is_same<M, rp::Merge>::value)
+                hipLaunchKernelGGL(k_rp64_merkle_subtree, grid, block, 0, st, children, out, n_children, s.levels);
+            else
+                hipLaunchKernelGGL(k_merkle_subtree<M>, grid, block, 0, st, children, out, n_children, s.levels);
+        } else if constexpr (PLAN.two_level) {  // MERKLE_LEVEL2
+            hipLaunchKernelGGL(k_merkle_level2<M>, grid, block, 0, st, children, out + n_par * M::NW, out + s.n_children * M::NW,
+                               s.n_children);
         }
-        children = (const uint32_t *)nodes + n_children * 8;  // that level lives at nodes[n .. 2n)
+        HIP_TRY(hipGetLastError());
+        n_children = s.n_children;
+        children = out + n_children * M::NW;  // that level lives at nodes[n .. 2n)
     }
     return 0;
 }
 
-// Sha3_256 tree: one lane per parent while a level still fills the chip (>= 2^15 parents, the one-lane-per-node rule of
-// run_merkle_dw), then the LDS subtree kernel, up to 9 levels per launch.  A pure kernel sequence like the BLAKE3 tree.
-static constexpr uint32_t SHA3_LEVEL_MIN_LOG = 15;
-static int run_merkle_sha3(hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes) {
-    const uint64_t *children = (const uint64_t *)leaves;
-    uint64_t n_children = n_leaves;
-    while (n_children > 1) {
-        const uint64_t n_par = n_children >> 1;
-        const uint32_t threads = 256;
-        const uint64_t grid = (n_par + threads - 1) / threads;
-        if (grid > 0x7FFFFFFFull) return fail(WF_ERR_ARG, "too many leaves for one launch");
-        if (n_par >= ((uint64_t)1 << SHA3_LEVEL_MIN_LOG)) {
-            hipLaunchKernelGGL(k_sha3_merkle_level, dim3((uint32_t)grid), dim3(threads), 0, st, (const ulonglong2 *)children,
-                               (ulonglong2 *)nodes + n_par * 2, n_par);
-            HIP_TRY(hipGetLastError());
-            n_children = n_par;
-        } else {
-            uint32_t total_levels = 0;
-            for (uint64_t t = n_children; t > 1; t >>= 1) total_levels++;
-            const uint32_t levels = std::min<uint32_t>(9, total_levels);
-            hipLaunchKernelGGL(k_sha3_merkle_subtree, dim3((uint32_t)grid), dim3(threads), 0, st, children, (uint64_t *)nodes,
-                               n_children, levels);
-            HIP_TRY(hipGetLastError());
-            n_children >>= levels;
-        }
-        children = (const uint64_t *)nodes + n_children * 4;  // that level lives at nodes[n .. 2n)
-    }
-    return 0;
-}
-
-// Rp64_256 tree: one lane per parent (rp::permute) while a level has at least 2^RP64_LEVEL_MIN_LOG parents, then the
-// lane-form subtree kernel (16 lanes per parent, rp::permute_lane), up to RP64_SUBTREE_LEVELS levels per launch.  The switch
-// is measured (docs/EXPERIMENTS.md "Rp64_256", scripts/rescue_bench.hip): a level of up to 2^16 parents costs one
-// permutation's latency with one lane per parent (0.33 ms), the lane form's latency is a ninth of that and its throughput
-// 73 %, so it wins up to 2^15 parents.  A pure kernel sequence like the other trees.
-static constexpr uint32_t RP64_LEVEL_MIN_LOG = 16;
-static int run_merkle_rp64(hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes) {
-    const uint64_t *children = (const uint64_t *)leaves;
-    uint64_t n_children = n_leaves;
-    while (n_children > 1) {
-        const uint64_t n_par = n_children >> 1;
-        if (n_par >= ((uint64_t)1 << RP64_LEVEL_MIN_LOG)) {
-            const uint32_t threads = 256;
-            const uint64_t grid = (n_par + threads - 1) / threads;
-            if (grid > 0x7FFFFFFFull) return fail(WF_ERR_ARG, "too many leaves for one launch");
-            hipLaunchKernelGGL(k_rp64_merkle_level, dim3((uint32_t)grid), dim3(threads), 0, st, (const ulonglong2 *)children,
-                               (ulonglong2 *)nodes + n_par * 2, n_par);
-            HIP_TRY(hipGetLastError());
-            n_children = n_par;
-        } else {
-            uint32_t total_levels = 0;
-            for (uint64_t t = n_children; t > 1; t >>= 1) total_levels++;
-            const uint32_t levels = std::min<uint32_t>(RP64_SUBTREE_LEVELS, total_levels);
-            const uint64_t grid = (n_par + RP64_SUBTREE_SPAN - 1) / RP64_SUBTREE_SPAN;
-            hipLaunchKernelGGL(k_rp64_merkle_subtree, dim3((uint32_t)grid), dim3(RP64_SUBTREE_THREADS), 0, st, children,
-                               (uint64_t *)nodes, n_children, levels);
-            HIP_TRY(hipGetLastError());
-            n_children >>= levels;
-        }
-        children = (const uint64_t *)nodes + n_children * 4;  // that level lives at nodes[n .. 2n)
-    }
-    return 0;
-}
-
-// dw: digest words -- 8 = Blake3_256, 6 = Blake3_192 (48-byte merge inputs; the slots' last two words are zeros)
-static int run_merkle(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes, uint32_t dw = 8,
-                      uint32_t hasher = WF_HASH_BLAKE3) {
-    if (hasher == WF_HASH_SHA3_256) return run_merkle_sha3(st, leaves, n_leaves, nodes);
-    if (hasher == WF_HASH_RP64_256) return run_merkle_rp64(st, leaves, n_leaves, nodes);
-    return dw == 6 ? run_merkle_dw<6>(ctx, st, leaves, n_leaves, nodes) : run_merkle_dw<8>(ctx, st, leaves, n_leaves, nodes);
+static int run_merkle(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes, uint32_t hasher,
+                      uint32_t digest_bytes) {
+    if (hasher == WF_HASH_SHA3_256) return run_merkle_plan<k3::Merge, MERKLE_PLAN_SHA3>(ctx, st, leaves, n_leaves, nodes);
+    if (hasher == WF_HASH_RP64_256) return run_merkle_plan<rp::Merge, MERKLE_PLAN_RP64>(ctx, st, leaves, n_leaves, nodes);
+    return digest_bytes == 24 ? run_merkle_plan<b3::Merge<6>, MERKLE_PLAN_BLAKE3>(ctx, st, leaves, n_leaves, nodes)
+                              : run_merkle_plan<b3::Merge<8>, MERKLE_PLAN_BLAKE3>(ctx, st, leaves, n_leaves, nodes);
 }
 
 // ------------------------------------------------------------------------------------------------- the path (device)
@@ -961,12 +892,12 @@ static int evaluate_and_commit(wf_ctx *ctx, hipStream_t st, const wf_params *p, 
     if (d_leaves) {
         if (!hashed) {
             prof_mark(ctx, st, "hash_rows");
-            rc = run_hash_rows<F>(ctx, st, d_lde, Nrows * row_width, Nrows, (uint32_t)row_width, base_cols, p->n_traces, d_leaves, p->digest_bytes / 4, p->hasher);
+            rc = run_hash_rows<F>(ctx, st, d_lde, Nrows * row_width, Nrows, (uint32_t)row_width, base_cols, p->n_traces, d_leaves, p->hasher, p->digest_bytes);
             if (rc) return rc;
         }
         if (d_nodes) {
             prof_mark(ctx, st, "merkle");
-            rc = run_merkle(ctx, st, d_leaves, Nrows, d_nodes, p->digest_bytes / 4, p->hasher);
+            rc = run_merkle(ctx, st, d_leaves, Nrows, d_nodes, p->hasher, p->digest_bytes);
             if (rc) return rc;
         }
     }
@@ -1216,7 +1147,7 @@ int wf_merkle_build_dev(wf_ctx *ctx, const void *d_leaves, size_t n_leaves, void
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     WF_ENTER(ctx, st);
     prof_mark(ctx, st, "merkle");
-    int rc = run_merkle(ctx, st, d_leaves, n_leaves, d_nodes, ctx->digest_bytes / 4, ctx->hasher);
+    int rc = run_merkle(ctx, st, d_leaves, n_leaves, d_nodes, ctx->hasher, ctx->digest_bytes);
     prof_mark(ctx, st, "between_calls");
     return rc;
 }
@@ -1437,9 +1368,9 @@ int wf_hash_rows(wf_ctx *ctx, uint32_t field, const void *rows, size_t n_rows, s
     hipStream_t st = ctx->stream;
     if (bytes) HIP_TRY(hipMemcpyAsync(ctx->io[2].p, rows, bytes, hipMemcpyHostToDevice, st));
     if (field == WF_FIELD_F64)
-        rc = run_hash_rows<F64>(ctx, st, ctx->io[2].p, 0, n_rows, (uint32_t)row_elems, (uint32_t)row_elems, 1, ctx->io[3].p, ctx->digest_bytes / 4, ctx->hasher);
+        rc = run_hash_rows<F64>(ctx, st, ctx->io[2].p, 0, n_rows, (uint32_t)row_elems, (uint32_t)row_elems, 1, ctx->io[3].p, ctx->hasher, ctx->digest_bytes);
     else
-        rc = run_hash_rows<F128>(ctx, st, ctx->io[2].p, 0, n_rows, (uint32_t)row_elems, (uint32_t)row_elems, 1, ctx->io[3].p, ctx->digest_bytes / 4, ctx->hasher);
+        rc = run_hash_rows<F128>(ctx, st, ctx->io[2].p, 0, n_rows, (uint32_t)row_elems, (uint32_t)row_elems, 1, ctx->io[3].p, ctx->hasher, ctx->digest_bytes);
     if (rc) return rc;
     if ((rc = path_digests_to_host(ctx, st, ctx->io[3].p, digests_out, n_rows, ctx->digest_bytes))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
@@ -1458,7 +1389,7 @@ int wf_merkle_build(wf_ctx *ctx, const uint8_t *leaves, size_t n_leaves, uint8_t
     if ((rc = ensure(ctx, ctx->io[4], n_leaves * 32))) return rc;
     hipStream_t st = ctx->stream;
     if ((rc = path_digests_from_host(ctx, st, leaves, ctx->io[3].p, n_leaves, ctx->digest_bytes))) return rc;
-    rc = run_merkle(ctx, st, ctx->io[3].p, n_leaves, ctx->io[4].p, ctx->digest_bytes / 4, ctx->hasher);
+    rc = run_merkle(ctx, st, ctx->io[3].p, n_leaves, ctx->io[4].p, ctx->hasher, ctx->digest_bytes);
     if (rc) return rc;
     if ((rc = path_digests_to_host(ctx, st, ctx->io[4].p, nodes_out, n_leaves, ctx->digest_bytes))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
@@ -1530,7 +1461,7 @@ static int trace_commit_sharded(wf_comm *c, const wf_params *p, const void *d_tr
     if (rc) return rc;
     const uint64_t n_local = N / W;
     if (n_local >= 2) {
-        rc = run_merkle(ctx, st, d_leaves, n_local, d_nodes, p->digest_bytes / 4);  // local layout: d_nodes[1] = this rank's sub-root
+        rc = run_merkle(ctx, st, d_leaves, n_local, d_nodes, WF_HASH_BLAKE3, p->digest_bytes);  // local layout: d_nodes[1] = this rank's sub-root
         if (rc) return rc;
     }
     // the top log2(W) levels: all-gather of the W sub-roots (32 * W bytes), folded by every rank
@@ -1542,7 +1473,7 @@ static int trace_commit_sharded(wf_comm *c, const wf_params *p, const void *d_tr
     } else {
         rc = comm_all_gather(c, sub_root, top + (size_t)W * 32, 32, st);
         if (rc) return rc;
-        rc = run_merkle(ctx, st, top + (size_t)W * 32, W, top, p->digest_bytes / 4);
+        rc = run_merkle(ctx, st, top + (size_t)W * 32, W, top, WF_HASH_BLAKE3, p->digest_bytes);
         if (rc) return rc;
     }
     prof_mark(ctx, st, "between_calls");
@@ -1601,13 +1532,13 @@ bool path_dense_column_ok(const wf_params *p) {
 bool path_dense_matrix_ok(const wf_params *p) { return dense_matrix_ok(p); }
 
 int path_hash_rows(wf_ctx *ctx, hipStream_t st, uint32_t field, const void *lde, uint64_t trace_elems, uint64_t n_rows,
-                   uint32_t row_width, uint32_t epr, uint32_t n_traces, void *leaves, uint32_t digest_bytes, uint32_t hasher) {
-    return field == WF_FIELD_F64 ? run_hash_rows<F64>(ctx, st, lde, trace_elems, n_rows, row_width, epr, n_traces, leaves, digest_bytes / 4, hasher)
-                                 : run_hash_rows<F128>(ctx, st, lde, trace_elems, n_rows, row_width, epr, n_traces, leaves, digest_bytes / 4, hasher);
+                   uint32_t row_width, uint32_t epr, uint32_t n_traces, void *leaves, uint32_t hasher, uint32_t digest_bytes) {
+    return field == WF_FIELD_F64 ? run_hash_rows<F64>(ctx, st, lde, trace_elems, n_rows, row_width, epr, n_traces, leaves, hasher, digest_bytes)
+                                 : run_hash_rows<F128>(ctx, st, lde, trace_elems, n_rows, row_width, epr, n_traces, leaves, hasher, digest_bytes);
 }
 
-int path_merkle(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes, uint32_t digest_bytes, uint32_t hasher) {
-    return run_merkle(ctx, st, leaves, n_leaves, nodes, digest_bytes / 4, hasher);
+int path_merkle(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes, uint32_t hasher, uint32_t digest_bytes) {
+    return run_merkle(ctx, st, leaves, n_leaves, nodes, hasher, digest_bytes);
 }
 
 int path_digests_to_host(wf_ctx *ctx, hipStream_t st, const void *d_slots, void *host, size_t n, uint32_t digest_bytes) {

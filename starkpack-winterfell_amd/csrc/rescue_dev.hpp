@@ -291,6 +291,20 @@ WF_HD void merge(const uint64_t (&in)[8], uint64_t (&out)[DIGEST]) {
     for (int i = 0; i < DIGEST; i++) out[i] = F64::to_canonical(s[RATE_AT + i]);
 }
 
+// The hasher as the tree kernels (Merge) and the lane-per-row leaf kernel (Absorb) take it: digests are four canonical
+// 64-bit words; the sponge absorbs the elements as they are stored (Montgomery residues), nothing is converted on the way in.
+struct Merge {
+    using W = uint64_t;
+    static constexpr int NW = DIGEST;
+    static constexpr bool HAS_QUAD = false;
+    static WF_HD void merge(const W (&in)[2 * NW], W (&out)[NW]) { rp::merge(in, out); }
+};
+struct Absorb {
+    static constexpr bool CANONICAL = false;
+    template <class Next>
+    static WF_HD void absorb(uint64_t n, Next &&next, uint64_t (&out)[DIGEST]) { hash_elements(n, next, out); }
+};
+
 // The lane form's start value of a merge: element i of the state before the permutation (w = the digest word i - 4).
 WF_HD uint64_t merge_lane_init(uint32_t i, uint64_t w) {
     return i == 0 ? elem_new(RATE) : (i >= (uint32_t)RATE_AT && i < (uint32_t)STATE) ? elem_new(w) : 0;

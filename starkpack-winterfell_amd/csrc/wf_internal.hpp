@@ -249,12 +249,13 @@ int path_constraint_commit(wf_ctx *ctx, const wf_params *p, const void *d_polys,
                            hipStream_t st, bool dense_rows = false);
 bool path_dense_column_ok(const wf_params *p);
 bool path_dense_matrix_ok(const wf_params *p);
-// (digest_bytes: 32 or 24; device leaves / nodes are 32-byte slots either way, a 24-byte digest in the first 24 bytes;
-// hasher: enum wf_hasher -- Sha3_256 goes to the kernels of keccak_kernels.hpp, Rp64_256 to those of rescue_kernels.hpp)
+// (hasher: enum wf_hasher -- every hasher's tree runs the kernels of kernels.hpp on its merge policy, the leaves of Sha3_256
+// and Rp64_256 come from keccak_kernels.hpp; digest_bytes: 32 or 24; device leaves / nodes are 32-byte slots either way, a
+// 24-byte digest in the first 24 bytes)
 int path_hash_rows(wf_ctx *ctx, hipStream_t st, uint32_t field, const void *lde, uint64_t trace_elems, uint64_t n_rows,
-                   uint32_t row_width, uint32_t epr, uint32_t n_traces, void *leaves, uint32_t digest_bytes, uint32_t hasher);
-int path_merkle(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes, uint32_t digest_bytes,
-                uint32_t hasher);
+                   uint32_t row_width, uint32_t epr, uint32_t n_traces, void *leaves, uint32_t hasher, uint32_t digest_bytes);
+int path_merkle(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes, uint32_t hasher,
+                uint32_t digest_bytes);
 // n digests from device slots to a HOST array of digest_bytes-sized entries (asynchronous on st; 24-byte digests are packed
 // on the device first) and the way back (host entries -> device slots)
 int path_digests_to_host(wf_ctx *ctx, hipStream_t st, const void *d_slots, void *host, size_t n, uint32_t digest_bytes);

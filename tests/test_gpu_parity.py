@@ -173,6 +173,30 @@ def test_merkle_build(ctx, orc, log_leaves):
     assert not got[0].any()
 
 
+@pytest.mark.parametrize("digest_bytes", [32, 24])
+@pytest.mark.parametrize("log_leaves,l2_min", [(19, None), (20, None), (16, 16)])
+def test_merkle_build_wide_levels(capi, orc, monkeypatch, log_leaves, l2_min, digest_bytes):
+    """The BLAKE3 tree kernels of the wide levels, at the smallest trees that reach them, for both digest sizes.  2^19 and
+    2^20 leaves: one k_merkle_level2 launch (its parents level has 2^18 / 2^19 nodes) and then k_merkle_subtree.  2^16
+    leaves on a context created with the tuning switch WF_EXP_MERKLE_L2_MIN=16: k_merkle_level at exactly 2^15 parents, the
+    only plan that takes the one-level kernel for BLAKE3."""
+    if l2_min is not None:
+        monkeypatch.setenv("WF_EXP_ENABLE", "1")  # the library reads its WF_EXP_* switches only under this one
+        monkeypatch.setenv("WF_EXP_MERKLE_L2_MIN", str(l2_min))
+    c = capi.Context(0)
+    try:
+        c.set_digest_bytes(digest_bytes)
+        rng = np.random.default_rng(100 * log_leaves + digest_bytes)
+        leaves = rng.integers(0, 256, size=(1 << log_leaves, digest_bytes), dtype=np.uint8)
+        with orc.digest_size(digest_bytes):
+            want = orc.build_merkle_nodes(leaves, threads=8)
+        got = c.merkle_build(leaves)
+        assert got.shape == want.shape and np.array_equal(got, want)
+        assert not got[0].any()
+    finally:
+        c.close()
+
+
 def test_error_codes(ctx, capi):
     """Preconditions the reference asserts on (SURVEY.md §8b 'Error convention') come back as status codes."""
     col = np.zeros(8, dtype=np.uint64)

@@ -116,8 +116,8 @@ def test_combined_rows_of_several_traces(capi, ctx, orc, n_traces, n_cols):
 
 
 # ---------------------------------------------------------------------------------------------------------- merkle_build
-# The switches of the Rescue tree (run_merkle_rp64, csrc/path.hip):
-#   a level of >= 2^16 parents (>= 2^17 children) is one k_rp64_merkle_level launch (one lane per parent): 2^15 and 2^16
+# The switches of the Rescue tree (MERKLE_PLAN_RP64, csrc/merkle_plan.hpp):
+#   a level of >= 2^16 parents (>= 2^17 children) is one k_merkle_level<rp::Merge> launch (one lane per parent): 2^15 and 2^16
 #   leaves below the switch, 2^17 at it (the switch is a measured one and came out one level above where a 2^16-leaf tree
 #   would still cross it);
 #   below that k_rp64_merkle_subtree (16 lanes per parent, 64 parents per work-group) folds up to 7 levels per launch:

@@ -68,9 +68,9 @@ def test_combined_rows_of_several_traces(capi, ctx, orc, field, logR, logB, n_tr
 
 
 # ---------------------------------------------------------------------------------------------------------- merkle_build
-# The switches of the Sha3 tree (run_merkle_sha3, csrc/path.hip; the same level switch as run_merkle_dw's one-lane-per-node rule):
-#   a level of >= 2^15 parents (>= 2^16 children) is one k_sha3_merkle_level launch: 2^15 leaves below, 2^16 at, 2^17 above;
-#   below that k_sha3_merkle_subtree folds up to 9 levels per launch: 2^8 (partial work-group, one launch), 2^9 (exactly
+# The switches of the Sha3 tree (MERKLE_PLAN_SHA3, csrc/merkle_plan.hpp; the same level switch as BLAKE3's one-lane-per-node rule):
+#   a level of >= 2^15 parents (>= 2^16 children) is one k_merkle_level<k3::Merge> launch: 2^15 leaves below, 2^16 at, 2^17 above;
+#   below that k_merkle_subtree<k3::Merge> folds up to 9 levels per launch: 2^8 (partial work-group, one launch), 2^9 (exactly
 #   nine levels, one launch), 2^10 (nine levels + a second launch of one level);
 #   2 and 4 leaves: a work-group of one and two active lanes.
 @pytest.mark.parametrize("log_n", [1, 2, 8, 9, 10, 15, 16, 17])
