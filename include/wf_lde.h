@@ -2,7 +2,9 @@
  * wf_lde.h -- C ABI of libwf_lde.so: MI355X (gfx950) implementation of the winter-prover hot path
  *   trace / constraint low-degree extension (radix-2 NTT over the f64 and f128 base fields, coset evaluation)
  *   + BLAKE3-256 Merkle commitment of the extended rows, including STARKPack's combined-row commitment
- *   (or Sha3_256, the reference's other byte-digest hasher, or Rp64_256, its Rescue Prime hasher over f64: enum wf_hasher).
+ *   (or Sha3_256, the reference's other byte-digest hasher, or Rp64_256, its Rescue Prime hasher over f64: enum wf_hasher),
+ *   the out-of-domain frame, the DEEP composition, FRI, the queries, and the proof-of-work nonce of the query seed
+ *   (wf_grind_seeds).  The channel's hashing of roots and its draws stay on the host.
  *
  * The reference (Rust) has no FFI layer; the seam these entry points replace is the pair of provided methods
  *   Prover::build_trace_commitment       /root/reference/prover/src/lib.rs:615-670
@@ -567,6 +569,23 @@ int wf_evaluate_polys_over(wf_ctx *ctx, const wf_params *p, const void *const *p
 int wf_hash_rows(wf_ctx *ctx, uint32_t field, const void *rows, size_t n_rows, size_t row_elems, uint8_t *digests_out);
 /* MerkleTree::new (crypto/src/merkle/mod.rs:117-136): leaves -> nodes (both n_leaves*32 bytes). */
 int wf_merkle_build(wf_ctx *ctx, const uint8_t *leaves, size_t n_leaves, uint8_t *nodes_out);
+
+/* ---- the proof-of-work of the query seed ------------------------------------------------------------------------ */
+
+/* ProverChannel::grind_query_seed (prover/src/channel.rs:182-198) for n_seeds independent coins: for seed i the SMALLEST
+ * nonce n with nonce_begin <= n, n - nonce_begin < max_nonces, whose merge_with_int(seed_i, n) has >= grinding_factor
+ * trailing zero bits in its first little-endian u64 (DefaultRandomCoin::check_leading_zeros).  seeds / new_seeds_out:
+ * 32-byte slots (a 24-byte digest in front, zeros behind); new_seeds_out[i] = merge_with_int(seed_i, nonce_i), the coin's
+ * seed after reseed_with_int.  found_out[i] = 1, or 0 with nonce 0 and a zero slot when the range holds no such nonce.
+ * The reference starts at 1 and allows grinding_factor <= 32 (air/src/options.rs:22).
+ * The hasher is the context's pair (wf_ctx_set_hasher / wf_ctx_set_digest_bytes), as for the FRI functions; seed words of
+ * an Rp64_256 context are read as BaseElement::new reads them.  The range ends at 2^64 - 1 at the latest (it never wraps).
+ * The search runs on the device in windows that double from a first one (2^16 or 2^20 nonces, by hasher) up to a
+ * per-hasher cap of a few milliseconds, the host looking at the result between two windows: the call is host-blocking (it returns with the answer) and cannot be captured into a graph.
+ * It is queued on the context's stream behind whatever the context was given before.
+ * WF_ERR_ARG: a null pointer, n_seeds outside 1..256, grinding_factor > 32, max_nonces == 0. */
+int wf_grind_seeds(wf_ctx *ctx, const uint8_t *seeds, size_t n_seeds, uint32_t grinding_factor, uint64_t nonce_begin,
+                   uint64_t max_nonces, uint64_t *nonces_out, uint8_t *new_seeds_out, uint8_t *found_out);
 
 #ifdef __cplusplus
 }

@@ -181,4 +181,12 @@ extern "C" {
         comm: *mut WfComm, p: *const WfParams, d_trace: *const c_void, d_polys: *mut c_void, d_lde_shard: *mut c_void,
         d_leaves: *mut c_void, d_nodes: *mut c_void, d_top: *mut c_void, stream: *mut c_void,
     ) -> c_int;
+    /// `ProverChannel::grind_query_seed` for `n_seeds` coins (1..=256): the smallest nonce of
+    /// `[nonce_begin, nonce_begin + max_nonces)` whose `merge_with_int(seed, nonce)` has `grinding_factor` (<= 32) trailing
+    /// zero bits, that digest (`new_seeds_out`: the coin's seed after `reseed_with_int`) and a found byte per seed.  Seeds
+    /// and new seeds are 32-byte slots; the hasher is the context's.  Host-blocking.
+    pub fn wf_grind_seeds(
+        ctx: *mut WfCtx, seeds: *const u8, n_seeds: usize, grinding_factor: u32, nonce_begin: u64, max_nonces: u64,
+        nonces_out: *mut u64, new_seeds_out: *mut u8, found_out: *mut u8,
+    ) -> c_int;
 }

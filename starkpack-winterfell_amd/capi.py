@@ -29,7 +29,7 @@ SYMBOLS = [
     "wf_fri_prover_commit_layer", "wf_fri_prover_fold", "wf_fri_prover_set_remainder", "wf_fri_prover_num_layers",
     "wf_fri_prover_layer", "wf_fri_prover_reset", "wf_fri_fold_positions",
     "wf_fft_evaluate_poly", "wf_fft_evaluate_poly_with_offset", "wf_fft_interpolate_poly",
-    "wf_fft_interpolate_poly_with_offset", "wf_evaluate_polys_over", "wf_hash_rows", "wf_merkle_build",
+    "wf_fft_interpolate_poly_with_offset", "wf_evaluate_polys_over", "wf_hash_rows", "wf_merkle_build", "wf_grind_seeds",
     "wf_comm_unique_id", "wf_comm_create", "wf_comm_create_with_transport", "wf_comm_destroy", "wf_comm_rank",
     "wf_comm_world", "wf_comm_rccl_version", "wf_comm_rccl_path", "wf_comm_stream_wait", "wf_comm_all_gather", "wf_comm_all_gather_roots", "wf_comm_barrier",
     "wf_comm_max_f64", "wf_comm_gather_f64", "wf_comm_info", "wf_shard_proofs", "wf_shard_cosets", "wf_shard_route", "wf_comm_all_gather_leaf_shards",
@@ -197,6 +197,7 @@ def load():
         L.wf_evaluate_polys_over.argtypes = [vp, PP, vp, vp]
         L.wf_hash_rows.argtypes = [vp, u32, vp, sz, sz, vp]
         L.wf_merkle_build.argtypes = [vp, vp, sz, vp]
+        L.wf_grind_seeds.argtypes = [vp, vp, sz, u32, C.c_uint64, C.c_uint64, vp, vp, vp]
         L.wf_device_count.argtypes = []
         L.wf_ctx_release_cached.argtypes = [vp]
         L.wf_ctx_set_digest_bytes.argtypes = [vp, u32]
@@ -604,6 +605,19 @@ class Context:
         nodes = np.empty_like(lv)
         _check(load().wf_merkle_build(self._h, _p(lv), lv.shape[0], _p(nodes)))
         return nodes
+
+    def grind(self, seeds, factor: int, nonce_begin: int = 1, max_nonces: int = 2**64 - 1):
+        """wf_grind_seeds (ProverChannel::grind_query_seed for every seed): seeds = (n, 32) bytes, 32-byte slots whatever the
+        digest size.  Returns (nonces, new_seeds, found): (n,) uint64 -- the smallest qualifying nonce of
+        [nonce_begin, nonce_begin + max_nonces), the range ending at 2^64 - 1 at the latest --, (n, 32) uint8 =
+        merge_with_int(seed, nonce), (n,) uint8; where nothing was found the nonce and the slot are zero."""
+        s = np.ascontiguousarray(seeds, dtype=np.uint8).reshape(-1, 32)
+        n = s.shape[0]
+        nonces = np.zeros(max(1, n), dtype=np.uint64)
+        new_seeds = np.zeros((max(1, n), 32), dtype=np.uint8)
+        found = np.zeros(max(1, n), dtype=np.uint8)
+        _check(load().wf_grind_seeds(self._h, _p(s), n, factor, nonce_begin, max_nonces, _p(nonces), _p(new_seeds), _p(found)))
+        return nonces[:n], new_seeds[:n], found[:n]
 
 
 class Commitment:

@@ -108,6 +108,24 @@ __device__ __forceinline__ void merge_slots(const uint32_t (&s)[16], uint32_t (&
     }
 }
 
+// Blake3_256::merge_with_int (blake/mod.rs:35-40, DW = 8: the hash of the 32-byte seed followed by the value as 8
+// little-endian bytes, 40 bytes) and Blake3_192::merge_with_int (blake/mod.rs:85-92, DW = 6: 24 + 8 = 32 bytes, truncated to
+// 24).  One compression either way; seed = the seed's 32-byte slot.  A caller that reads out[0] alone pays for nothing else
+// of the last round's output.
+template <int DW>
+__device__ __forceinline__ void merge_with_int(const uint32_t (&seed)[8], uint64_t value, uint32_t (&out)[8]) {
+    uint32_t m[16];
+#pragma unroll
+    for (int i = 0; i < DW; i++) m[i] = seed[i];
+    m[DW] = (uint32_t)value;
+    m[DW + 1] = (uint32_t)(value >> 32);
+#pragma unroll
+    for (int i = DW + 2; i < 16; i++) m[i] = 0;
+    set_iv(out);
+    compress(out, m, 0, 0, 4 * DW + 8, CHUNK_START | CHUNK_END | ROOT);
+    if constexpr (DW == 6) out[6] = out[7] = 0;
+}
+
 // ---- the same merge by FOUR lanes (a quad): lane q holds column q of the 4 x 4 state (a = v[q], b = v[4+q], c = v[8+q],
 // d = v[12+q]); the column step is lane-local, the diagonal step reaches the neighbours' b, c, d through DPP quad permutes.
 // A third of the instructions per lane (about 230 against 678): for the narrow top levels of a Merkle tree, where one

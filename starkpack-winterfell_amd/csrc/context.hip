@@ -1,4 +1,4 @@
-// libwf_lde.so, unit 1 of 6 -- the context: errors, the registry of live contexts, the buffer pool, profiling marks,
+// libwf_lde.so, unit 1 of 7 -- the context: errors, the registry of live contexts, the buffer pool, profiling marks,
 // column upload / download, parameter validation and the size helpers of the C ABI (include/wf_lde.h).
 // There is deliberately no CPU fallback: every compute entry point needs a HIP device.
 #include "wf_internal.hpp"
@@ -69,6 +69,14 @@ wf_tuning tuning_from_env() {
     if (const char *e = getenv("WF_EXP_FAIL_AFTER_SEGMENT")) {  // error-path test of the pipelined upload
         const int v = atoi(e);
         if (v >= 0 && v < 4096) t.fail_after_segment = v;
+    }
+    if (const char *e = getenv("WF_EXP_GRIND_WINDOW_LOG2")) {
+        const int v = atoi(e);
+        if (v >= 2 && v <= 30) t.grind_window_log2 = (uint32_t)v;
+    }
+    if (const char *e = getenv("WF_EXP_GRIND_WINDOW_CAP_LOG2")) {
+        const int v = atoi(e);
+        if (v >= 2 && v <= 30) t.grind_window_cap_log2 = (uint32_t)v;
     }
     return t;
 }
@@ -387,6 +395,7 @@ void wf_ctx_destroy(wf_ctx *ctx) {
         if (b.p) (void)hipFree(b.p);
     if (ctx->hash_tmp.p) (void)hipFree(ctx->hash_tmp.p);
     if (ctx->tickets.p) (void)hipFree(ctx->tickets.p);
+    if (ctx->grind.p) (void)hipFree(ctx->grind.p);
     if (ctx->pack_tmp.p) (void)hipFree(ctx->pack_tmp.p);
     {
         std::lock_guard<std::mutex> lock(ctx->pool_mutex);  // (nobody can be inside pool_free any more: the context is retired)

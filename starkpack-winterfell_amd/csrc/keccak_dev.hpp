@@ -107,6 +107,22 @@ WF_HD void sha3_merge(const uint64_t (&in)[8], uint64_t (&out)[4]) {
     for (int i = 0; i < 4; i++) out[i] = s[i];
 }
 
+// Sha3_256::merge_with_int (sha/mod.rs:32-37): SHA3-256 of the seed's 32 bytes followed by the value as 8 little-endian
+// bytes = five message lanes, the padding in the same block.
+WF_HD void merge_with_int(const uint64_t (&seed)[4], uint64_t value, uint64_t (&out)[4]) {
+    uint64_t s[25];
+#pragma unroll
+    for (int i = 0; i < 4; i++) s[i] = seed[i];
+    s[4] = value;
+    s[5] = 0x06;
+#pragma unroll
+    for (int i = 6; i < 25; i++) s[i] = 0;
+    s[16] = 0x80ull << 56;
+    keccak_f(s);
+#pragma unroll
+    for (int i = 0; i < 4; i++) out[i] = s[i];
+}
+
 // SHA3-256 of a message of n_lanes 8-byte lanes; next() returns them in order (each a little-endian 64-bit word of the
 // message).  One permutation call site: the loop runs once per rate block, the last block carries the padding -- a message
 // that fills its last block exactly (n_lanes a multiple of 17) gets a further block that holds only the padding.  State

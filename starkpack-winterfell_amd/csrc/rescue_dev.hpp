@@ -291,6 +291,34 @@ WF_HD void merge(const uint64_t (&in)[8], uint64_t (&out)[DIGEST]) {
     for (int i = 0; i < DIGEST; i++) out[i] = F64::to_canonical(s[RATE_AT + i]);
 }
 
+// merge_with_int (rescue/rp64_256/mod.rs:194-215) on a seed already in Montgomery form (the search kernel converts its
+// seed once): the seed in rate places 0..3, BaseElement::new(value) in place 4 and state[0] = 5 when value < p; otherwise
+// value / p in place 5 as well and state[0] = 6.  p <= value < 2^64 < 2 p, so that quotient is 1.  Equal to hash_elements
+// of those 5 or 6 elements.  out = the canonical digest words.
+WF_HD void merge_with_int_mont(const uint64_t (&seed)[DIGEST], uint64_t value, uint64_t (&out)[DIGEST]) {
+    const bool wide = value >= F64::P;
+    uint64_t s[STATE];
+    s[0] = elem_new(wide ? 6 : 5);
+#pragma unroll
+    for (int i = 1; i < RATE_AT; i++) s[i] = 0;
+#pragma unroll
+    for (int i = 0; i < DIGEST; i++) s[RATE_AT + i] = seed[i];
+    s[RATE_AT + 4] = elem_new(value);
+    s[RATE_AT + 5] = wide ? F64::one() : 0;
+    s[RATE_AT + 6] = s[RATE_AT + 7] = 0;
+    permute(s);
+#pragma unroll
+    for (int i = 0; i < DIGEST; i++) out[i] = F64::to_canonical(s[RATE_AT + i]);
+}
+
+// The same on the seed's digest words as stored (canonical, or any u64 from a caller: read as BaseElement::new reads them).
+WF_HD void merge_with_int(const uint64_t (&seed)[DIGEST], uint64_t value, uint64_t (&out)[DIGEST]) {
+    uint64_t m[DIGEST];
+#pragma unroll
+    for (int i = 0; i < DIGEST; i++) m[i] = elem_new(seed[i]);
+    merge_with_int_mont(m, value, out);
+}
+
 // The hasher as the tree kernels (Merge) and the lane-per-row leaf kernel (Absorb) take it: digests are four canonical
 // 64-bit words; the sponge absorbs the elements as they are stored (Montgomery residues), nothing is converted on the way in.
 struct Merge {

@@ -6,6 +6,7 @@
 //   fri.hip       FRI layer commitments and the resident FRI prover
 //   comm.hip      wf_comm: RCCL / caller transport, partition rules
 //   deep.hip      DEEP composition polynomial
+//   grind.hip     the nonce search of the query seed (wf_grind_seeds)
 // A function that launches kernels lives in exactly one unit (kernels are templates / static functions of the headers, so
 // each is compiled once, where it is launched); the other units reach it through the non-template entry points below.
 #pragma once
@@ -77,6 +78,8 @@ struct wf_tuning {
     bool no_gtab = false;             // WF_EXP_NO_GTAB: later wide strided passes rebuild their output factors in LDS per tile
     uint32_t wide_ti = 0;             // WF_EXP_WIDE_TI: inner positions per tile of the wide strided pass of 3+-pass plans (2, 4, 8); 1 = never; 0 = planner's own (2)
     int fail_after_segment = -1;      // WF_EXP_FAIL_AFTER_SEGMENT: the pipelined upload fails after that many segments (error-path test)
+    uint32_t grind_window_log2 = 0;      // WF_EXP_GRIND_WINDOW_LOG2: log2 of the nonce search's first window (2..30); 0 = the hasher's own (grind_plan.hpp)
+    uint32_t grind_window_cap_log2 = 0;  // WF_EXP_GRIND_WINDOW_CAP_LOG2: log2 of its largest window (2..30); 0 = the hasher's own
 };
 wf_tuning tuning_from_env();
 
@@ -102,6 +105,7 @@ struct wf_ctx {
     DevBuf scratch;   // evaluation intermediate [cosets][columns][R]
     DevBuf io[5];     // staging for the host-buffer API: trace, polys, lde, leaves, nodes
     DevBuf hash_tmp;  // chunk chaining values of rows longer than one BLAKE3 chunk
+    DevBuf grind;     // wf_grind_seeds: seeds, best[], outputs (a few KiB)
     DevBuf tickets;   // per-XCD ticket + exit counters of the persistent last passes (self-resetting; cleared again after any reported failure)
     uint64_t tickets_epoch = 0;  // fail_epoch() when the counters were last cleared
     // Buffers of destroyed resident commitments, kept for the next commitment of the same shape (four hipFree + four
