@@ -251,6 +251,9 @@ struct Sha3_256 {
 struct Rp64_256 {  // f64 matrices only; a digest is ElementDigest::as_bytes (four canonical little-endian u64)
     static constexpr uint32_t ID = WF_HASH_RP64_256;
 };
+struct RpJive64_256 {  // the same rules as Rp64_256; merge is one width-8 permutation with the Jive sum
+    static constexpr uint32_t ID = WF_HASH_RPJIVE64_256;
+};
 
 class Prover {
   public:

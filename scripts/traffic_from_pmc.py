@@ -44,7 +44,8 @@ LOGICAL = [
     # (k_merkle_level<wf::b3::Merge<8>>, <wf::k3::Merge>, <wf::rp::Merge>): the substrings take every hasher's, and
     # k_rp64_merkle_subtree (the lane-form top of the Rp64_256 tree) is listed so that the Sha3_256 and Rp64_256 trees fall
     # into this group whole, deliberately.  cfg 2 (BLAKE3) launches k_merkle_level2 x3 and k_merkle_subtree x2 as before.
-    ("merkle", ["k_merkle_level", "k_merkle_subtree", "k_rp64_merkle_subtree"])
+    # (k_rpjive_merkle_subtree: the same for the RpJive64_256 tree)
+    ("merkle", ["k_merkle_level", "k_merkle_subtree", "k_rp64_merkle_subtree", "k_rpjive_merkle_subtree"])
 ]
 # Round 4 calibration: the SECOND strided evaluation pass of cfg 3 must read the 17.18 GB intermediate exactly once (nothing can
 # absorb 16 GiB); its raw counter is 8.59 GB -- with 64-byte tile rows (round 3's kernel, same raw figure) as with 128-byte rows.

@@ -14,6 +14,7 @@
 #include "grind_plan.hpp"
 #include "keccak_dev.hpp"
 #include "rescue_dev.hpp"
+#include "rescue_jive_dev.hpp"
 
 namespace wf {
 
@@ -89,6 +90,22 @@ struct GrindRp64 {
     }
     static __device__ __forceinline__ void digest(const Seed &s, uint64_t nonce, uint64_t (&out)[4]) {
         rp::merge_with_int_mont(s.w, nonce, out);
+    }
+};
+
+// RpJive64_256, the one-lane-per-permutation form (rpj::permute): the seed read, converted once and kept in scalar registers
+// exactly as GrindRp64 does; merge_with_int is the Jive compression of seed || nonce (rpj::merge_with_int_mont).
+struct GrindRpJive {
+    typedef GrindRp64::Seed Seed;
+    static __device__ __forceinline__ void prepare(const uint64_t *slot, Seed &s) { GrindRp64::prepare(slot, s); }
+    static __device__ __forceinline__ void wave_uniform(Seed &s) { GrindRp64::wave_uniform(s); }
+    static __device__ __forceinline__ uint32_t head32(const Seed &s, uint64_t nonce) {
+        uint64_t d[4];
+        rpj::merge_with_int_mont(s.w, nonce, d);
+        return (uint32_t)d[0];
+    }
+    static __device__ __forceinline__ void digest(const Seed &s, uint64_t nonce, uint64_t (&out)[4]) {
+        rpj::merge_with_int_mont(s.w, nonce, out);
     }
 };
 

@@ -29,6 +29,11 @@ constexpr GrindPlan GRIND_PLAN_SHA3 = {16, 24, GRIND_LANE_ITERS};
 // (4096 x 1: 2.61 ms) -- presumably the waves of a SIMD then sit in different phases of the permutation; the cause was not
 // examined further.  A work-group that starts behind the answer leaves at once, so nothing is lost for the early exit.
 constexpr GrindPlan GRIND_PLAN_RP64 = {16, 20, 1};
+// RpJive64_256 (scripts/time_grind.py rpjive64_256, profiles/rpjive_rescue_bench.txt): one permutation's latency is 0.22 ms,
+// which 2^16 nonces still cost (0.219 ms; 2^17: 0.277, 2^18: 0.487, 2^19: 0.896); 2^20 are 1.71 ms (0.614 G nonces/s, 100 % of
+// the register-only loop of the width-8 permutation; 2^21 would be 3.4 ms).  The same three numbers as Rp64_256 come out; one
+// nonce per lane is taken over from it and was not measured again.
+constexpr GrindPlan GRIND_PLAN_RPJIVE = {16, 20, 1};
 
 struct GrindWindow {
     uint64_t base, count;  // nonces base .. base + count - 1; count == 0: the range is spent

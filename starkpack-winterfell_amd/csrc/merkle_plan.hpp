@@ -26,6 +26,16 @@ constexpr MerklePlan MERKLE_PLAN_SHA3 = {false, 15, 0, 9, 256, 256};
 // with one lane per parent (0.33 ms), the lane form's latency is a ninth of that and its throughput 73 %, so it wins up to
 // 2^15 parents.
 constexpr MerklePlan MERKLE_PLAN_RP64 = {false, 16, 0, 7, 64, 1024};
+// RpJive64_256: the sub-tree kernel is the lane form with 8 lanes per parent and none idle (rpj::merge_lane), so a
+// work-group of 1024 lanes spans 128 parents and folds 8 levels.  The switch is measured (docs/EXPERIMENTS.md
+// "RpJive64_256", scripts/rescue_jive_bench.hip, profiles/rpjive_rescue_bench.txt).  One level, ms, lane per parent / lane
+// form: 2^13 0.219 / 0.068, 2^14 0.219 / 0.071, 2^15 0.224 / 0.075, 2^16 0.230 / 0.131, 2^17 0.297 / 0.238, 2^18 0.507 / 0.443,
+// 2^20 1.694 / 1.649, 2^22 6.491 / 6.505: with no idle lanes the lane form runs at 97-98 % of the other form's register-only
+// rate (Rp64_256: 73 %), so a single level only crosses over at 2^22.  What a launch of eight levels loses on its idle waves
+// moves the best switch of a whole tree down: 2^23 leaves 14.23 / 13.99 / 14.16 / 14.51 ms with the lane-per-parent kernel
+// from 2^16 / 2^17 / 2^18 / 2^19 parents up, 2^18 leaves 1.170 / 1.086 ms from 2^16 / 2^17; two earlier sessions order them
+// the same way (14.49 / 14.26 / 14.46 / 14.77; 1.165 / 1.090 and 1.192 / 1.105).
+constexpr MerklePlan MERKLE_PLAN_RPJIVE = {false, 17, 0, 8, 128, 1024};
 
 enum MerkleLaunch : uint32_t { MERKLE_LEVEL2, MERKLE_LEVEL, MERKLE_SUBTREE };
 
