@@ -145,3 +145,51 @@ def pattern_columns(rng, field: int, n_cols: int, n: int, ext: int = 1, first: i
     """n_cols columns of n rows, the patterns of PATTERNS in turn from number `first` on: neighbouring columns of one matrix (the
     lanes of a packed row, the columns of a segment) hold different patterns."""
     return [pattern_column(rng, field, PATTERNS[(first + c) % len(PATTERNS)], n, ext) for c in range(n_cols)]
+
+
+def single_at(field: int, n: int, ext: int, index: int) -> np.ndarray:
+    """One column of n rows of `ext` coordinates: zeros, and p - 1 in every coordinate of row `index`."""
+    rows = [0] * n
+    rows[index] = MODULUS[field] - 1
+    return elements(field, [v for v in rows for _ in range(ext)])
+
+
+def edge_scalars(field: int) -> list:
+    """0, 1 and p - 1 as stored (any value below p is an element; 1 is Montgomery one() for f64), and -1."""
+    p = MODULUS[field]
+    minus_one = (p - 1) * R64 % p if field == F64 else p - 1
+    return sorted({0, ONE[field], p - 1, minus_one, 1})
+
+
+def edge_points(field: int, ext: int) -> list:
+    """Elements of the degree-`ext` extension: (v, 0, ..) for the edge scalars, and for ext > 1 a single non-zero coordinate
+    elsewhere (base part 0)."""
+    pts = [[v] + [0] * (ext - 1) for v in edge_scalars(field)]
+    for k in range(1, ext):
+        for v in (ONE[field], MODULUS[field] - 1):
+            pt = [0] * ext
+            pt[k] = v
+            pts.append(pt)
+    return [elements(field, pt) for pt in pts]
+
+
+def edge_points_nonzero(field: int, ext: int) -> list:
+    """edge_points without the zero element (the points with base part 0 and another coordinate set stay)."""
+    return [pt for pt in edge_points(field, ext) if pt.any()]
+
+
+def commit_resident_with_polys(ctx, orc, params, polys: list, ext: int):
+    """A resident trace commitment whose polynomials are the given coefficient vectors.  trace_commit_resident takes
+    evaluations and interpolates them; field arithmetic is exact, so the oracle's evaluations of `polys` over the trace domain
+    (no offset) come back as `polys`, which is asserted on the polynomials the call returns.  -> the commitment."""
+    field, n = params.field, 1 << params.log2_trace_len
+    tw = orc.get_twiddles(field, n)
+    cols = []
+    for p in polys:
+        v = p.copy()
+        orc.evaluate_poly(field, v, n, ext, tw)
+        cols.append(v)
+    com, got = ctx.trace_commit_resident(params, cols, want_polys=True)
+    for c, (g, p) in enumerate(zip(got, polys)):
+        assert np.array_equal(g, p), f"resident polynomial {c} is not the chosen coefficient vector"
+    return com

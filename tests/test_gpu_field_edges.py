@@ -109,25 +109,6 @@ def test_trace_commit_on_edge_patterns(ctx, orc, capi, field, ext, logR, logB, n
 
 
 # ------------------------------------------------------------------------------------------------ FRI folding
-def _edge_scalars(field):
-    """0, 1 and p - 1 as stored (any value below p is an element; 1 is Montgomery one() for f64), and -1."""
-    p = E.MODULUS[field]
-    minus_one = (p - 1) * E.R64 % p if field == F64 else p - 1
-    return sorted({0, E.ONE[field], p - 1, minus_one, 1})
-
-
-def _edge_points(field, ext):
-    """Elements of the degree-`ext` extension: (v, 0, ..) for the edge scalars, and for ext > 1 a single non-zero coordinate
-    elsewhere (base part 0)."""
-    pts = [[v] + [0] * (ext - 1) for v in _edge_scalars(field)]
-    for k in range(1, ext):
-        for v in (E.ONE[field], E.MODULUS[field] - 1):
-            pt = [0] * ext
-            pt[k] = v
-            pts.append(pt)
-    return [E.elements(field, pt) for pt in pts]
-
-
 @pytest.mark.parametrize("field,ext", FIELD_EXT)
 @pytest.mark.parametrize("folding", [2, 4, 8, 16])
 def test_fri_apply_drp_with_edge_alphas(ctx, orc, field, ext, folding):
@@ -135,7 +116,7 @@ def test_fri_apply_drp_with_edge_alphas(ctx, orc, field, ext, folding):
     rows = 512   # the domain is a power of two; several work-groups
     values = E.alphabet_draw(rng, field, rows * folding * ext)
     offset = OFFSETS[field][0]
-    for alpha in _edge_points(field, ext):
+    for alpha in E.edge_points(field, ext):
         want = orc.apply_drp(field, values, rows, ext, folding, offset, alpha)
         got = ctx.fri_apply_drp(field, ext, values, folding, offset, alpha)
         assert np.array_equal(got, want), f"alpha {alpha.tolist()}"
@@ -149,7 +130,7 @@ def test_evaluate_columns_at_edge_points(ctx, orc, field, ext_c, ext_z, logn):
     rng = np.random.default_rng(_seed("ood", field, ext_c, ext_z, logn))
     n = 1 << logn
     cols = [E.alphabet_draw(rng, field, n * ext_c) for _ in range(2)] + [E.pattern_column(rng, field, "pm1", n, ext_c)]
-    for z in _edge_points(field, ext_z):
+    for z in E.edge_points(field, ext_z):
         got = ctx.evaluate_columns_at(field, ext_c, cols, z, ext_z)
         for i, c in enumerate(cols):
             assert np.array_equal(got[i], orc.eval_column_at(field, c, ext_c, z, ext_z)), f"column {i}, z {z.tolist()}"

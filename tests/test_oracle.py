@@ -275,15 +275,15 @@ def test_apply_drp_equals_coefficient_folding(orc, N):
     poly = [rnd.randrange(p) for _ in range(n // 2)] + [0] * (n // 2)
     g = F.root_of_unity(6)
     ev = [P.poly_eval(poly, off * pow(g, i, p) % p, p) for i in range(n)]
-    alpha = rnd.randrange(p)
-    folded = [sum(pow(alpha, j, p) * poly[N * i + j] for j in range(N)) % p for i in range(n // N)]
     g2 = F.root_of_unity((n // N).bit_length() - 1)
-    want = [P.poly_eval(folded, pow(off, N, p) * pow(g2, i, p) % p, p) for i in range(n // N)]
     mem = lambda v: np.array([F.to_mem(x) for x in v], dtype=np.uint64)  # noqa: E731
     tr = orc.transpose_slice(F64, mem(ev), n, 1, N)
     assert [int(v) for v in tr[:N]] == [F.to_mem(ev[j * (n // N)]) for j in range(N)]   # utils/core/src/lib.rs:206-227
-    got = orc.apply_drp(F64, tr, n // N, 1, N, off, mem([alpha]))
-    assert [F.from_mem(int(v)) for v in got] == want
+    for alpha in (rnd.randrange(p), 0, 1, p - 1):   # alpha = 0 keeps every N-th coefficient (0^0 = 1)
+        folded = [sum(pow(alpha, j, p) * poly[N * i + j] for j in range(N)) % p for i in range(n // N)]
+        want = [P.poly_eval(folded, pow(off, N, p) * pow(g2, i, p) % p, p) for i in range(n // N)]
+        got = orc.apply_drp(F64, tr, n // N, 1, N, off, mem([alpha]))
+        assert [F.from_mem(int(v)) for v in got] == want, alpha
 
 
 def test_extension_products(orc):
@@ -313,7 +313,88 @@ def test_extension_products(orc):
     assert not orc.ext_mul(F64, 2, r, mem([0, 0])).any()
 
 
-@pytest.mark.parametrize("field,ext", [(F64, 1), (F64, 2), (F64, 3), (F128, 1), (F128, 2)])
+class _ExtInts:
+    """Schoolbook arithmetic of the degree-`ext` extension on lists of Python integers, and the conversions between those
+    (canonical values) and the oracle's arrays -- independent of the oracle's field code."""
+
+    def __init__(self, orc, field, ext):
+        self.field, self.ext = field, ext
+        self.p = p = P64 if field == F64 else P128
+        if field == F64:
+            r_inv = pow(2**64, -1, p)
+            self.to_mem = lambda vals: np.array([(v << 64) % p for v in vals], dtype=np.uint64)
+            self.from_mem = lambda a: [int(v) * r_inv % p for v in np.asarray(a).reshape(-1)]
+        else:
+            self.to_mem = orc.f128_from_ints
+            self.from_mem = lambda a: orc.f128_to_ints(np.asarray(a).reshape(-1, 2))
+
+    def mul(self, a, b):
+        ext, p = self.ext, self.p
+        c = [0] * (2 * ext - 1)
+        for i in range(ext):
+            for j in range(ext):
+                c[i + j] += a[i] * b[j]
+        if ext == 2 and self.field == F64:  # x^2 = x - 2
+            c = [c[0] - 2 * c[2], c[1] + c[2]]
+        elif ext == 2:                      # x^2 = x + 1
+            c = [c[0] + c[2], c[1] + c[2]]
+        elif ext == 3:                      # x^3 = x + 1, x^4 = x^2 + x
+            c = [c[0] + c[3], c[1] + c[3] + c[4], c[2] + c[4]]
+        return [v % p for v in c]
+
+    def add(self, a, b):
+        return [(x + y) % self.p for x, y in zip(a, b)]
+
+    def sub(self, a, b):
+        return [(x - y) % self.p for x, y in zip(a, b)]
+
+    def embed(self, v):
+        return [v] + [0] * (self.ext - 1)
+
+    def horner(self, coeffs, x):  # coeffs: list of E
+        acc = [0] * self.ext
+        for c in reversed(coeffs):
+            acc = self.add(self.mul(acc, x), c)
+        return acc
+
+    def rows(self, mem, ext_c):
+        """An array of n * ext_c base elements -> n elements of E (a base-field column embedded)."""
+        v = self.from_mem(mem)
+        return [v[i * ext_c:(i + 1) * ext_c] + [0] * (self.ext - ext_c) for i in range(len(v) // ext_c)]
+
+
+def _trace_generator(orc, field, logn):
+    """The generator of the trace domain as a Python integer: the reference's get_root_of_unity(log2 n)."""
+    p = P64 if field == F64 else P128
+    if field == F64:
+        g = int(orc.lib().orc_f64_get_root_of_unity(logn)) * pow(2**64, -1, p) % p
+    else:
+        g = orc.f128_root_of_unity(logn)
+    assert pow(g, 1 << logn, p) == 1 and pow(g, 1 << (logn - 1), p) == p - 1
+    return g
+
+
+def _assert_deep_identity(A, d_e, tables_int, cc_t, cons_int, cc_c, z, g, xs):
+    """D(x) (x - z)(x - z g) = sum_i cc_i [(T_i(x) - T_i(z))(x - z g) + (T_i(x) - T_i(z g))(x - z)]
+    + sum_i cc'_i (H_i(x) - H_i(z))(x - z g) at every x of xs.  tables_int: one list of columns (lists of E) per table."""
+    zg = A.mul(z, A.embed(g))
+    for x in xs:
+        lhs = A.mul(A.horner(d_e, x), A.mul(A.sub(x, z), A.sub(x, zg)))
+        rhs = [0] * A.ext
+        for cols, cc in zip(tables_int, cc_t):
+            for col, k in zip(cols, cc):
+                tx, tz, tzg = A.horner(col, x), A.horner(col, z), A.horner(col, zg)
+                term = A.add(A.mul(A.sub(tx, tz), A.sub(x, zg)), A.mul(A.sub(tx, tzg), A.sub(x, z)))
+                rhs = A.add(rhs, A.mul(k, term))
+        for col, k in zip(cons_int, cc_c):
+            rhs = A.add(rhs, A.mul(k, A.mul(A.sub(A.horner(col, x), A.horner(col, z)), A.sub(x, zg))))
+        assert lhs == rhs, (z, x)
+
+
+FIELD_EXT = [(F64, 1), (F64, 2), (F64, 3), (F128, 1), (F128, 2)]
+
+
+@pytest.mark.parametrize("field,ext", FIELD_EXT)
 def test_deep_composition_is_the_sum_of_the_quotients(orc, field, ext):
     """DeepCompositionPoly (prover/src/composer/mod.rs:52-66,156-167): the composed polynomial D satisfies, at a random
     point x of E,  D(x) (x - z)(x - z g) = sum_i cc_i [(T_i(x) - T_i(z))(x - z g) + (T_i(x) - T_i(z g))(x - z)]
@@ -321,43 +402,14 @@ def test_deep_composition_is_the_sum_of_the_quotients(orc, field, ext):
     field code."""
     import random
     rnd = random.Random(field * 10 + ext)
-    p = P64 if field == F64 else P128
-
-    def emul(a, b):
-        c = [0] * (2 * ext - 1)
-        for i in range(ext):
-            for j in range(ext):
-                c[i + j] += a[i] * b[j]
-        if ext == 2 and field == F64:      # x^2 = x - 2
-            c = [c[0] - 2 * c[2], c[1] + c[2]]
-        elif ext == 2:                     # x^2 = x + 1
-            c = [c[0] + c[2], c[1] + c[2]]
-        elif ext == 3:                     # x^3 = x + 1, x^4 = x^2 + x
-            c = [c[0] + c[3], c[1] + c[3] + c[4], c[2] + c[4]]
-        return [v % p for v in c]
-
-    eadd = lambda a, b: [(x + y) % p for x, y in zip(a, b)]  # noqa: E731
-    esub = lambda a, b: [(x - y) % p for x, y in zip(a, b)]  # noqa: E731
-
-    def horner(coeffs, x):  # coeffs: list of E
-        acc = [0] * ext
-        for c in reversed(coeffs):
-            acc = eadd(emul(acc, x), c)
-        return acc
-
-    if field == F64:
-        to_mem = lambda vals: np.array([(v << 64) % p for v in vals], dtype=np.uint64)  # noqa: E731
-        from_mem = lambda a: [int(v) * pow(2**64, -1, p) % p for v in np.asarray(a).reshape(-1)]  # noqa: E731
-    else:
-        to_mem = orc.f128_from_ints
-        from_mem = lambda a: orc.f128_to_ints(np.asarray(a).reshape(-1, 2))  # noqa: E731
-    embed = lambda v: [v] + [0] * (ext - 1)  # noqa: E731
+    A = _ExtInts(orc, field, ext)
+    p, to_mem = A.p, A.to_mem
     n = 32
     rand_e = lambda: [rnd.randrange(p) for _ in range(ext)]  # noqa: E731
     # two packed traces: main columns over the base field, auxiliary ones over E; two composition columns
     tables_int = []
     for _ in range(2):
-        main = [[embed(rnd.randrange(p)) for _ in range(n)] for _ in range(3)]
+        main = [[A.embed(rnd.randrange(p)) for _ in range(n)] for _ in range(3)]
         aux = [[rand_e() for _ in range(n)] for _ in range(2 if ext > 1 else 0)]
         tables_int.append((main, aux))
     cons_int = [[rand_e() for _ in range(n)] for _ in range(2)]
@@ -368,34 +420,67 @@ def test_deep_composition_is_the_sum_of_the_quotients(orc, field, ext):
               for m, a in tables_int]
     cons = [to_mem([v for c in col for v in c]) for col in cons_int]
     d = orc.deep_compose(field, ext, n, tables, cons, to_mem(z), [to_mem(c) for tab in cc_t for c in tab], [to_mem(c) for c in cc_c])
-    d_int = from_mem(d)
+    d_int = A.from_mem(d)
     d_e = [d_int[i * ext:(i + 1) * ext] for i in range(n)]
     assert d_e[n - 1] == [0] * ext and d_e[n - 2] != [0] * ext      # degree n - 2 (composer/mod.rs:151)
-    if field == F64:  # the generator of the trace domain: the reference's get_root_of_unity(log2 n)
-        g = int(orc.lib().orc_f64_get_root_of_unity(5)) * pow(2**64, -1, p) % p
-    else:
-        g = orc.f128_root_of_unity(5)
-    assert pow(g, n, p) == 1 and pow(g, n // 2, p) == p - 1
-    zg = emul(z, embed(g))
-    for _ in range(3):
-        x = rand_e()
-        lhs = emul(horner(d_e, x), emul(esub(x, z), esub(x, zg)))
-        rhs = [0] * ext
-        for (m, a), cc in zip(tables_int, cc_t):
-            for col, k in zip(m + a, cc):
-                tx, tz, tzg = horner(col, x), horner(col, z), horner(col, zg)
-                term = eadd(emul(esub(tx, tz), esub(x, zg)), emul(esub(tx, tzg), esub(x, z)))
-                rhs = eadd(rhs, emul(k, term))
-        for col, k in zip(cons_int, cc_c):
-            rhs = eadd(rhs, emul(k, emul(esub(horner(col, x), horner(col, z)), esub(x, zg))))
-        assert lhs == rhs
+    g = _trace_generator(orc, field, 5)
+    _assert_deep_identity(A, d_e, [m + a for m, a in tables_int], cc_t, cons_int, cc_c, z, g, [rand_e() for _ in range(3)])
+
+
+@pytest.mark.parametrize("field,ext", FIELD_EXT)
+def test_deep_composition_is_the_sum_of_the_quotients_on_edge_operands(orc, field, ext):
+    """The same identity on the operand classes of tests/test_gpu_proof_edges.py, where the oracle is the GPU's reference:
+    columns drawn from the limb alphabet, all p - 1, a single entry, zero; composition coefficients 0, one, p - 1 and alphabet
+    draws; z at every non-zero edge point and at g^-1 (the second divisor is then x - 1).  The result may be of lower degree
+    than n - 2 here, or zero: only the top coefficient is asserted."""
+    import random
+    import edge_util as E
+    rnd = random.Random(field * 10 + ext)
+    rng = np.random.default_rng(field * 10 + ext)
+    A = _ExtInts(orc, field, ext)
+    p, n = A.p, 32
+    g = _trace_generator(orc, field, 5)
+
+    def column(kind, ext_c):
+        return E.single_at(field, n, ext_c, 17) if kind == "single_17" else E.pattern_column(rng, field, kind, n, ext_c)
+
+    main_kinds = [("alphabet", "pm1", "single_17"), ("zero", "single_last", "alphabet")]
+    aux_kinds = [("alphabet", "single_0"), ("pm1", "zero")] if ext > 1 else [(), ()]
+    tables = [[(column(k, 1), 1) for k in mk] + [(column(k, ext), ext) for k in ak] for mk, ak in zip(main_kinds, aux_kinds)]
+    cons = [column("alphabet", ext), column("single_last", ext)]
+    one = E.elements(field, [E.ONE[field]] + [0] * (ext - 1))
+    coeff_cycle = [E.elements(field, [0] * ext), one, E.elements(field, [p - 1] * ext)]
+    n_coeffs = sum(len(t) for t in tables) + len(cons)
+    coeffs = [coeff_cycle[i % 4] if i % 4 < 3 else E.alphabet_draw(rng, field, ext) for i in range(n_coeffs)]
+    cc_t_mem, cc_c_mem = coeffs[:n_coeffs - len(cons)], coeffs[n_coeffs - len(cons):]
+    g_inv = A.to_mem(A.embed(pow(g, -1, p)))
+    tables_int = [[A.rows(col, ext_c) for col, ext_c in t] for t in tables]
+    cons_int = [A.rows(c, ext) for c in cons]
+    it = iter(cc_t_mem)
+    cc_t = [[A.from_mem(next(it)) for _ in t] for t in tables]
+    cc_c = [A.from_mem(c) for c in cc_c_mem]
+    points = E.edge_points_nonzero(field, ext) + [g_inv]
+    assert len(points) >= 3
+    for z_mem in points:
+        d = orc.deep_compose(field, ext, n, tables, cons, z_mem, cc_t_mem, cc_c_mem)
+        d_int = A.from_mem(d)
+        d_e = [d_int[i * ext:(i + 1) * ext] for i in range(n)]
+        assert d_e[n - 1] == [0] * ext
+        xs = [[rnd.randrange(p) for _ in range(ext)] for _ in range(2)]
+        _assert_deep_identity(A, d_e, tables_int, cc_t, cons_int, cc_c, A.from_mem(z_mem), g, xs)
+    # all coefficients zero: the zero polynomial
+    zero = [E.elements(field, [0] * ext)] * n_coeffs
+    d = orc.deep_compose(field, ext, n, tables, cons, points[0], zero[:len(cc_t_mem)], zero[len(cc_t_mem):])
+    assert not d.any()
 
 
 @pytest.mark.parametrize("field", [F64, F128])
 def test_acc_column_divides_by_the_divisor(orc, field):
     """acc_column + get_inv_evaluation (prover/src/constraints/evaluation_table.rs:335-426): for every point x_i = offset g^i
     of the constraint evaluation domain, result[i] (x_i^a - b) = column[i] prod_k (x_i - e_k) -- on Python integers; and the
-    zero of a divisor's numerator inside the domain leaves a zero (math::batch_inversion ignores zeros)."""
+    zero of a divisor's numerator inside the domain leaves a zero (math::batch_inversion ignores zeros).  Then on the operands
+    of tests/test_gpu_proof_edges.py: b an edge scalar, eight exemption points, the numerator vanishing at i = 0 and i = nz - 1,
+    and with a > 1, where the zero repeats with period nz = ce / a."""
     import random
     rnd = random.Random(field)
     p = P64 if field == F64 else P128
@@ -408,23 +493,53 @@ def test_acc_column_divides_by_the_divisor(orc, field):
         to_mem = orc.f128_from_ints
         from_mem = lambda a: orc.f128_to_ints(np.asarray(a).reshape(-1, 2))  # noqa: E731
         g = orc.f128_root_of_unity(6)
-    for a, n_ex in [(16, 2), (1, 0), (4, 0), (64, 1)]:
-        b = rnd.randrange(1, p)
-        ex = [rnd.randrange(p) for _ in range(n_ex)]
-        col = [rnd.randrange(p) for _ in range(ce * ext)]
+
+    def check(a, b, ex, col, ext):
+        """-> the indices at which the numerator vanishes (the result is zero there)."""
         got = from_mem(orc.combine_evaluation_table(field, ext, [to_mem(col)], [(a, to_mem([b]), to_mem(ex) if ex else None)], off))
+        zeros = []
         for i in range(ce):
             x = off * pow(g, i, p) % p
             e = 1
             for v in ex:
                 e = e * (x - v) % p
+            num = (pow(x, a, p) - b) % p
+            if num == 0:
+                zeros.append(i)
             for w in range(ext):
-                assert got[i * ext + w] * (pow(x, a, p) - b) % p == col[i * ext + w] * e % p
+                if num == 0:
+                    assert got[i * ext + w] == 0
+                else:
+                    assert got[i * ext + w] * num % p == col[i * ext + w] * e % p
+        return zeros
+
+    for a, n_ex in [(16, 2), (1, 0), (4, 0), (64, 1)]:
+        b = rnd.randrange(1, p)
+        ex = [rnd.randrange(p) for _ in range(n_ex)]
+        assert check(a, b, ex, [rnd.randrange(p) for _ in range(ce * ext)], ext) == []
     # b = (offset g^5)^1: the numerator vanishes at i = 5 -> the inverse there is taken as zero
     b = off * pow(g, 5, p) % p
     col = [rnd.randrange(1, p) for _ in range(ce)]
     got = from_mem(orc.combine_evaluation_table(field, 1, [to_mem(col)], [(1, to_mem([b]), None)], off))
     assert got[5] == 0 and all(v != 0 for i, v in enumerate(got) if i != 5)
+    # the operand classes of tests/test_gpu_proof_edges.py.  Edge values are edges of the stored form: converted from it
+    import edge_util as E
+    rng = np.random.default_rng(field)
+    edge = [v for v in from_mem(E.elements(field, E.edge_scalars(field))) if v]
+    alphabet_col = lambda: from_mem(E.alphabet_draw(rng, field, ce * ext))  # noqa: E731
+    for k, b in enumerate(edge):                             # numerator constants 1, -1, and what the stored 1 and p - 1 stand for
+        ex8 = (edge + from_mem(E.alphabet_draw(rng, field, 8)))[:8]   # MAX_EXEMPTIONS exemption points, 0 not among them ..
+        ex8[7] = 0                                                    # .. but for this one
+        assert len(ex8) == 8
+        a = (16, 1, 64, 4)[k % 4]
+        assert check(a, b, ex8 if k % 2 == 0 else [], alphabet_col(), ext) == []   # (none of these b is an x^a of the domain)
+    for a in (1, 4, 16):                                     # the numerator vanishes at i, and for a > 1 with period nz = ce / a
+        nz = ce // a
+        for i in (0, nz - 1):
+            b = pow(off * pow(g, i, p), a, p)
+            ex = from_mem(E.alphabet_draw(rng, field, 8)) if a == 4 else []
+            assert check(a, b, ex, alphabet_col(), ext) == list(range(i, ce, nz))
+    assert check(1, edge[0], [], [p - 1] * (ce * ext), ext) == []   # a column of p - 1
 
 
 # ------------------------------------------------------------------------------------ golden: the reference's own inputs
