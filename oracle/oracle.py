@@ -84,6 +84,12 @@ def lib():
         L.orc_deep_compose.argtypes = [i32, sz, sz, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp]
         L.orc_transpose_slice.argtypes = [i32, vp, sz, sz, sz, vp]
         L.orc_apply_drp.argtypes = [i32, vp, sz, sz, sz, vp, vp, vp, i32]
+        L.orc_rescue_permute.argtypes = [vp, vp, sz, i32]
+        L.orc_rescue_hash_rows.argtypes = [vp, vp, sz, sz, sz, vp, i32]
+        L.orc_rescue_merge.argtypes = [vp, vp, vp]
+        L.orc_rescue_merge_with_int.argtypes = [vp, vp, u64, vp]
+        L.orc_rescue_merkle_nodes.argtypes = [vp, vp, sz, vp, i32]
+        L.orc_rescue_grind.argtypes = [vp, vp, C.c_uint, u64, u64, vp, vp, i32]
         _lib = L
     return _lib
 
@@ -587,3 +593,73 @@ def combine_evaluation_table(field: int, ext: int, columns, divisors, offset: in
         lib().orc_acc_column(field, _p(col), ext, ce, a, _p(bb), _p(exs) if exs is not None else None, n_ex,
                              _p(_off_bytes(offset)), _p(result))
     return result
+
+
+# ----------------------------------------------------------------------------------------------- Rescue Prime (plain reference)
+
+class Rescue:
+    """oracle/rescue_ref.c for one hasher: Rescue("rp64_256") or Rescue("rpjive64_256").  The parameters are read from
+    tests/golden/<name>_params.json and handed to every call; the C file holds none.  Digests are 32 bytes (four canonical
+    little-endian u64).  threads = 0: min(orc_max_threads(), 16)."""
+
+    KINDS = {"rp64_256": 0, "rpjive64_256": 1}
+
+    def __init__(self, name: str, params_path: str | None = None):
+        import json
+        path = params_path or os.path.join(os.path.dirname(_HERE), "tests", "golden", f"{name}_params.json")
+        prm = json.load(open(path))
+        self.name, self.width, self.rate_at = name, prm["state_width"], prm["rate_range"][0]
+        assert prm["modulus"] == 2**64 - 2**32 + 1 and prm["digest_range"] == [4, 8]
+        words = [self.KINDS[name], self.width, self.rate_at, prm["num_rounds"], prm["alpha"], prm["inv_alpha"]]
+        words += prm["mds_row"] + [x for r in prm["ark1"] for x in r] + [x for r in prm["ark2"] for x in r]
+        assert len(words) == 6 + self.width * (1 + 2 * prm["num_rounds"])
+        self._prm = np.array(words, dtype=np.uint64)
+
+    @staticmethod
+    def _check(rc):
+        if rc < 0:
+            raise ValueError(f"rescue reference refused its arguments: {rc}")
+        return rc
+
+    def permute(self, states, threads: int = 0) -> np.ndarray:
+        """(n, width) canonical integers (any u64 is reduced) -> the permuted states."""
+        s = np.array(states, dtype=np.uint64).reshape(-1, self.width)
+        self._check(lib().orc_rescue_permute(_p(self._prm), _p(s), s.shape[0], threads))
+        return s
+
+    def hash_rows(self, rows, threads: int = 0) -> np.ndarray:
+        """(n, len) stored (Montgomery) residues -> (n, 32) digests."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        assert r.ndim == 2
+        out = np.empty((r.shape[0], 32), dtype=np.uint8)
+        self._check(lib().orc_rescue_hash_rows(_p(self._prm), _p(r), r.shape[0], r.shape[1], r.shape[1], _p(out), threads))
+        return out
+
+    def merge(self, a: bytes, b: bytes) -> bytes:
+        w = np.frombuffer(bytes(a) + bytes(b), dtype="<u8").astype(np.uint64)
+        assert w.size == 8
+        out = np.empty(32, dtype=np.uint8)
+        self._check(lib().orc_rescue_merge(_p(self._prm), _p(w), _p(out)))
+        return out.tobytes()
+
+    def merge_with_int(self, seed: bytes, value: int) -> bytes:
+        w = np.frombuffer(bytes(seed), dtype="<u8").astype(np.uint64)
+        assert w.size == 4 and 0 <= value < 2**64
+        out = np.empty(32, dtype=np.uint8)
+        self._check(lib().orc_rescue_merge_with_int(_p(self._prm), _p(w), value, _p(out)))
+        return out.tobytes()
+
+    def merkle_nodes(self, leaves, threads: int = 0) -> np.ndarray:
+        lv = np.ascontiguousarray(leaves, dtype=np.uint8).reshape(-1, 32)
+        nodes = np.empty_like(lv)
+        self._check(lib().orc_rescue_merkle_nodes(_p(self._prm), _p(lv), lv.shape[0], _p(nodes), threads))
+        return nodes
+
+    def grind(self, seed: bytes, factor: int, begin: int = 1, max_nonces: int = 2**64 - 1, threads: int = 0):
+        """(nonce, digest) of the smallest qualifying nonce of [begin, begin + max_nonces) (clipped at 2^64 - 1), or
+        (None, None)."""
+        w = np.frombuffer(bytes(seed), dtype="<u8").astype(np.uint64)
+        assert w.size == 4 and 0 <= begin < 2**64 and 0 < max_nonces < 2**64
+        nonce, out = C.c_uint64(0), np.empty(32, dtype=np.uint8)
+        rc = self._check(lib().orc_rescue_grind(_p(self._prm), _p(w), factor, begin, max_nonces, C.byref(nonce), _p(out), threads))
+        return (int(nonce.value), out.tobytes()) if rc else (None, None)

@@ -1,6 +1,7 @@
 // libwf_field_probe.so -- test helper, NOT part of the product ABI (nothing in include/wf_lde.h, nothing in libwf_lde.so
 // uses it; same footing as libwf_yardstick.so): the field primitives of field.hpp, the extension products of
-// fri_kernels.hpp and the Rescue S-boxes of rescue_dev.hpp as the DEVICE compiler emits them, one element per thread, so
+// fri_kernels.hpp, the Rescue S-boxes of rescue_dev.hpp and the MDS rows of both Rescue hashers (one-lane form, every row of
+// one state, no round constants) as the DEVICE compiler emits them, one element per thread, so
 // that tests/test_gpu_field_probe.py can feed the 32-bit carry and borrow chains the operands that make their rare
 // branches fire and compare every result with integer arithmetic.
 //
@@ -12,6 +13,7 @@
 #include "field.hpp"
 #include "fri_kernels.hpp"
 #include "rescue_dev.hpp"
+#include "rescue_jive_dev.hpp"
 
 using namespace wf;
 
@@ -33,7 +35,9 @@ enum Op {
     OP_EXT_MUL_F128_2 = 12,
     OP_RP_POW7 = 13,
     OP_RP_INV_SBOX = 14,
-    OP_COUNT = 15
+    OP_RP_MDS_ROWS = 15,   // 12 words in, 12 out: out[i] = rp::mds_row(i) of the state
+    OP_RPJ_MDS_ROWS = 16,  // 8 words in, 8 out: out[i] = rpj::mds_row(i) of the state
+    OP_COUNT = 17
 };
 
 // mul_pow2<1..63> | div_pow2<1..32> | neg_div_pow2<1..32> | neg_mul_pow2<33..63> | mul_pow2_192<0..191>
@@ -82,6 +86,8 @@ constexpr Shape shape_of(int op) {
         case OP_EXT_MUL_F64_2: return {2, 2, 2};
         case OP_EXT_MUL_F64_3: return {3, 3, 3};
         case OP_EXT_MUL_F128_2: return {4, 4, 4};
+        case OP_RP_MDS_ROWS: return {rp::STATE, 0, rp::STATE};
+        case OP_RPJ_MDS_ROWS: return {rpj::STATE, 0, rpj::STATE};
         default: return {0, 0, 0};
     }
 }
@@ -124,6 +130,19 @@ __global__ void __launch_bounds__(256) k_probe(const uint64_t *__restrict__ a, c
         probe_ext_mul<F128, 2>((const U128 *)pa, (const U128 *)pb, (U128 *)po);
     else if constexpr (OP == OP_RP_POW7) po[0] = rp::pow7(pa[0]);
     else if constexpr (OP == OP_RP_INV_SBOX) po[0] = rp::lane_inv_sbox(pa[0]);
+    else if constexpr (OP == OP_RP_MDS_ROWS) {
+        uint64_t s[rp::STATE];
+#pragma unroll
+        for (int j = 0; j < rp::STATE; j++) s[j] = pa[j];
+#pragma unroll
+        for (int i = 0; i < rp::STATE; i++) po[i] = rp::mds_row((uint32_t)i, [&](uint32_t j) { return s[j]; });
+    } else if constexpr (OP == OP_RPJ_MDS_ROWS) {
+        uint64_t s[rpj::STATE];
+#pragma unroll
+        for (int j = 0; j < rpj::STATE; j++) s[j] = pa[j];
+#pragma unroll
+        for (int i = 0; i < rpj::STATE; i++) po[i] = rpj::mds_row((uint32_t)i, [&](uint32_t j) { return s[j]; });
+    }
 }
 
 template <int OP>

@@ -7,6 +7,12 @@
 //   M w0 .. w7     merge of two digests; the words are taken as a caller hands them in (any u64, reduced as BaseElement::new)
 //   L w0 .. w7     merge through the lane form's host code (merge_lanes_host: t = init + fin per lane, lanes 0..3 add lane + 4)
 //   I s0 .. s3 v   merge_with_int of the seed words (any u64) and the 64-bit value v
+//   D i f y0 .. y7 the linear layer alone on a state of raw residues (what stands behind the first S-box): 8 words of mds_ark
+//                  (one-lane form) then 8 of lane_mds_ark (lane form), both with ARK1 of round 0, as raw residues.  f = 1
+//                  marks a state built so that the closing addition of row i wraps (tests/rescue_edge_util.py, case 1):
+//                  mds_row_plain_plus below, a copy of mds_row that ends in a plain +, must differ from mds_row there.
+//                  Once a D request was seen, the program FAILS (exit 4) unless such states told the copy from the real
+//                  function on every row -- as test_field_edges.cpp does for the wrong-mask reduction.
 //   T              the tables as the header holds them: 56 ARK1 words, 56 ARK2 words (Montgomery form), 8 MDS entries
 //   K              MERKLE_PLAN_RPJIVE through merkle_next_launch for n_leaves = 2^1 .. 2^34 and the CU counts of
 //                  test_merkle_plan.cpp: prints <sequences checked> <violations>
@@ -71,7 +77,23 @@ static void check_plan() {
     print_words(out, 2);
 }
 
+// rpj::mds_row with its closing canonical addition replaced by a plain 64-bit +: the mistake the directed states exist for.
+template <class Get>
+static uint64_t mds_row_plain_plus(uint32_t i, Get &&get) {
+    uint64_t lo = 0, hi = 0;
+    for (int k = 0; k < rpj::STATE; k++) {
+        uint32_t j = i + (uint32_t)k;
+        j -= j >= (uint32_t)rpj::STATE ? (uint32_t)rpj::STATE : 0u;
+        const uint64_t v = get(j);
+        lo += (uint64_t)rpj::mds_coef(k) * (uint32_t)v;
+        hi += (uint64_t)rpj::mds_coef(k) * (uint32_t)(v >> 32);
+    }
+    const uint64_t top = hi >> 32;
+    return (hi << 32) + (lo + ((top << 32) - top));
+}
+
 int main() {
+    bool directed_seen = false, told_apart[rpj::STATE] = {};
     std::string line;
     std::vector<std::string> lines;
     int c;
@@ -134,6 +156,29 @@ int main() {
             for (int i = 0; i < 4; i++) s[i] = w[i];
             rpj::merge_with_int(s, w[4], d);
             print_words(d, 4);
+        } else if (op == 'D') {
+            constexpr int W = rpj::STATE;
+            if (w.size() != 2 + (size_t)W || w[0] >= (uint64_t)W || w[1] > 1) {
+                fprintf(stderr, "D needs a row, a flag and %d words\n", W);
+                return 2;
+            }
+            uint64_t s[W], m[W], o[2 * W];
+            for (int i = 0; i < W; i++) {
+                s[i] = w[2 + i];
+                if (s[i] >= F64::P) {
+                    fprintf(stderr, "D takes raw residues below p\n");
+                    return 2;
+                }
+            }
+            auto get = [&](uint32_t j) { return s[j]; };
+            for (int i = 0; i < W; i++) m[i] = s[i];
+            rpj::mds_ark(m, 0, 0);
+            for (int i = 0; i < W; i++) o[i] = m[i];
+            for (int i = 0; i < W; i++) o[W + i] = rpj::lane_mds_ark((uint32_t)i, 0, 0, get);
+            directed_seen = true;
+            const uint32_t row = (uint32_t)w[0];
+            if (w[1] && mds_row_plain_plus(row, get) != rpj::mds_row(row, get)) told_apart[row] = true;
+            print_words(o, 2 * W);
         } else if (op == 'T') {
             std::vector<uint64_t> t;
             for (int half = 0; half < 2; half++)
@@ -146,6 +191,14 @@ int main() {
         } else {
             fprintf(stderr, "unknown request %c\n", op);
             return 2;
+        }
+    }
+    if (directed_seen) {
+        for (int i = 0; i < rpj::STATE; i++) {
+            if (!told_apart[i]) {
+                fprintf(stderr, "no case-1 state told mds_row from its plain-+ copy on row %d\n", i);
+                return 4;
+            }
         }
     }
     return 0;

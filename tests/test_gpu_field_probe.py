@@ -26,7 +26,7 @@ F64, F128 = E.F64, E.F128
 P, Q = E.P64, E.P128
 (OP_F64_MUL, OP_F64_ADD, OP_F64_SUB, OP_F64_MONT_REDUCE, OP_F64_TO_CANONICAL, OP_F64_FROM_CANONICAL, OP_F64_SHIFTS,
  OP_F128_ADD, OP_F128_SUB, OP_F128_MUL, OP_EXT_MUL_F64_2, OP_EXT_MUL_F64_3, OP_EXT_MUL_F128_2, OP_RP_POW7,
- OP_RP_INV_SBOX) = range(15)
+ OP_RP_INV_SBOX, OP_RP_MDS_ROWS, OP_RPJ_MDS_ROWS) = range(17)
 POISON = 0xA5A5A5A5A5A5A5A5
 TAIL = 333  # poisoned elements behind the n the kernel may write
 
@@ -199,6 +199,46 @@ def test_rescue_sboxes(probe):
     inv = probe(OP_RP_INV_SBOX, x).reshape(-1)
     assert inv.tolist() == [pow(c, R.INV_ALPHA, P) * 2**64 % P for c in can]
     assert np.array_equal(probe(OP_RP_INV_SBOX, p7).reshape(-1), x)
+
+
+@pytest.mark.parametrize("entry,op", [("rp_state", OP_RP_MDS_ROWS), ("rpj_state", OP_RPJ_MDS_ROWS)])
+def test_rescue_mds_rows_directed(probe, entry, op):
+    """rp::mds_row / rpj::mds_row, every row of one state per thread (the one-lane form, no round constants), on the directed
+    states of tests/rescue_edge_util.py: for every output row the five cases of the closing canonical addition (the 64-bit
+    sum wraps; is 2^64; is p; is p - 1; lies in (p, 2^64)), the two states that give the largest hi and the largest lo,
+    mixed with uniform states.  Compared with the integer row product.  The lane form is not probed here (its gathers need
+    full waves): tests/test_gpu_rescue_full.py runs it in the sub-tree kernels."""
+    import rescue_edge_util as D
+    row = D.PARAMS[D.ENTRY[entry][0]]["mds_row"]
+    w = len(row)
+    assert D.reachable(entry) == D.all_pairs(entry)   # every (row, case): nothing is left out silently
+    directed = [D.directed_set(entry)[rc] for rc in D.all_pairs(entry)]
+    # a plain + in place of the canonical addition is wrong on the wrapping states, in the row they were built for
+    for (i, case), y in zip(D.all_pairs(entry), directed):
+        assert (D.mds_row_plain_plus(row, y, i) != D.mds_row_value(row, y, i)) == (case in ("wrap", "wrap0", "p", "above_p"))
+    rng = np.random.default_rng(w)
+    states = np.concatenate([E.u64([v for y in directed + D.extra_states(w) for v in y]).reshape(-1, w),
+                             rand_f64(rng, 1001 * w).reshape(-1, w)])
+    order = rng.permutation(_ragged(states.shape[0]))
+    states = np.ascontiguousarray(states[order])
+    got = probe(op, states)
+    assert got.shape == (states.shape[0], w)
+    want = [[D.mds_row_value(row, y, i) for i in range(w)] for y in states.tolist()]
+    assert got.tolist() == want
+    assert probe(OP_F64_ADD, [0], [0]).tolist() == [[0]]   # (the op table is still in step: an old op after the new ones)
+
+
+def test_probe_words_cover_every_op(probe):
+    """wf_field_probe_words knows the two new ops and nothing past them."""
+    import starkpack_winterfell_amd.build as b
+    lib = C.CDLL(b.field_probe_path())
+    wa, wb, wo = C.c_int(), C.c_int(), C.c_int()
+    words = {}
+    for op in range(-1, 19):
+        if lib.wf_field_probe_words(op, C.byref(wa), C.byref(wb), C.byref(wo)) == 1:
+            words[op] = (wa.value, wb.value, wo.value)
+    assert sorted(words) == list(range(17))
+    assert words[OP_RP_MDS_ROWS] == (12, 0, 12) and words[OP_RPJ_MDS_ROWS] == (8, 0, 8) and words[OP_RP_INV_SBOX] == (1, 0, 1)
 
 
 @pytest.mark.parametrize("n", [1, 63, 65, 255, 257, 1000])

@@ -9,10 +9,16 @@
      crypto/src/merkle/tests.rs:67-92                             tree == nested merges
      crypto/src/hash/blake/tests.rs:11-30                         hash is sensitive to zero padding
 """
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
 import golden_util as G
+import rp64_util as RP
+import rpjive_util as RJ
 from conftest import rand_f64, rand_f128
 
 F64, F128 = 1, 2
@@ -619,3 +625,142 @@ def test_reference_held_known_answers(orc):
     tr = orc.transpose_slice(F64, np.array(c["values"], dtype=np.uint64), len(c["values"]), 1, c["N"])
     assert tr.reshape(-1, c["N"]).tolist() == c["expected"], c["where"]
 
+
+
+# ------------------------------------------------------------------------------------------------ Rescue: the plain C reference
+# oracle/rescue_ref.c (orc.Rescue) is what tests/test_gpu_rescue_full.py compares whole trees with.  Here it is pinned to
+# the Python-integer restatements (rp64_util, rpjive_util) and the two known answers, every test inside their budget of
+# 2048 Python permutations.
+RESCUE = {"rp64_256": RP, "rpjive64_256": RJ}
+RESCUE_ROW_LENGTHS = {"rp64_256": [1, 7, 8, 9, 15, 16, 17, 24, 25, 255],       # tests/test_gpu_rp64.py
+                      "rpjive64_256": [1, 3, 4, 5, 7, 8, 9, 12, 13, 255]}      # tests/test_gpu_rpjive.py
+RESCUE_EDGES = [0, 1, P64 - 1, 2**32 - 1]
+
+
+@pytest.fixture(params=sorted(RESCUE))
+def rescue(request, orc):
+    """(name, the C reference, the Python reference); the Python side stays inside 2048 permutations per test."""
+    U = RESCUE[request.param]
+    before = U.PERMUTATIONS
+    yield request.param, orc.Rescue(request.param), U
+    assert U.PERMUTATIONS - before <= 2048
+
+
+def _rescue_edge_states(w):
+    """The edge states of tests/test_rescue_host.py and tests/test_rpjive_host.py."""
+    states = [[e] * w for e in RESCUE_EDGES]
+    for k in range(4):
+        states.append([RESCUE_EDGES[(i + k) % 4] for i in range(w)])
+    states.append([P64 - 1] * (w - 1) + [0])
+    return states
+
+
+def test_rescue_ref_permutation(rescue):
+    name, A, U = rescue
+    w = A.width
+    kat = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", f"{name}_kat.json")))
+    assert A.permute([kat["input"]])[0].tolist() == kat["expected"]
+    rng = np.random.default_rng(41)
+    states = _rescue_edge_states(w) + rng.integers(0, P64, size=(100, w), dtype=np.uint64).tolist()
+    states.append([P64, P64 + 1, 2**64 - 1, 2**64 - 2**32] * (w // 4))   # words at and above p are reduced on the way in
+    got = A.permute(states)
+    assert got.shape == (len(states), w) and (got < np.uint64(P64)).all()
+    for s, g in zip(states, got):
+        assert g.tolist() == U.permute(s)
+    # the threaded and the single-threaded run are the same function (above 64 states the batch is split)
+    many = rng.integers(0, P64, size=(300, w), dtype=np.uint64)
+    assert np.array_equal(A.permute(many, threads=1), A.permute(many))
+
+
+def test_rescue_ref_hash_rows(rescue):
+    name, A, U = rescue
+    rng = np.random.default_rng(42)
+    for n in RESCUE_ROW_LENGTHS[name]:
+        rows = rand_f64(rng, 3 * n).reshape(3, n)
+        if n != 255:
+            rows[0, :] = 0
+            rows[1, :] = np.uint64(P64 - 1)
+        else:
+            rows = rows[:1]
+        got = A.hash_rows(rows)
+        assert got.shape == (rows.shape[0], 32) and (got.view(np.uint64) < np.uint64(P64)).all()
+        assert np.array_equal(got, U.hash_rows(rows)), n
+    # the count is part of the hash; 100 rows go through the threaded loop
+    rows = rand_f64(rng, 100 * 5).reshape(100, 5)
+    got = A.hash_rows(rows)
+    assert np.array_equal(got, A.hash_rows(rows, threads=1)) and np.array_equal(got[::9], U.hash_rows(rows[::9]))
+    assert not np.array_equal(A.hash_rows(rows[:, :4]), A.hash_rows(np.hstack([rows[:, :4], np.zeros((100, 1), dtype=np.uint64)])))
+
+
+def test_rescue_ref_merge_and_tree(rescue):
+    name, A, U = rescue
+    rng = np.random.default_rng(43)
+
+    def dig(words):
+        return b"".join(int(x).to_bytes(8, "little") for x in words)
+
+    merges = [[int(x) for x in rng.integers(0, 2**64, size=8, dtype=np.uint64)] for _ in range(4)]
+    merges += [[0] * 8, [P64 - 1] * 8, [2**64 - 1] * 8, [P64, P64 + 1, 2**64 - 1, 2**64 - 2**32, 0, 1, P64 - 1, 2**32 - 1]]
+    for m in merges:
+        got = A.merge(dig(m[:4]), dig(m[4:]))
+        assert got == U.merge(dig(m[:4]), dig(m[4:])), m
+        assert got == A.merge(dig([x % P64 for x in m[:4]]), dig([x % P64 for x in m[4:]]))   # words are read reduced
+        assert all(x < P64 for x in U.digest_words(got))
+    # both branches of merge_with_int, a seed with words >= p
+    import grind_util as GU
+    for seed in (dig([P64, 2**64 - 1, P64 + 1, 0x0123456789ABCDEF]), hashlib.sha256(b"grind seed 0").digest()):
+        for v in [0, 1, 2**32 - 1, 2**32, P64 - 1, P64, P64 + 1, P64 + 2, 2**64 - 1]:
+            want = GU.merge_with_int(None, "rp64_256", seed, v) if name == "rp64_256" else RJ.merge_with_int(seed, v)
+            assert A.merge_with_int(seed, v) == want, v
+    # a 2^6-leaf tree (63 merges), leaves with words >= p; the threaded levels (2^8 leaves) equal the serial ones
+    leaves = rng.integers(0, 2**64, size=(64, 4), dtype=np.uint64)
+    leaves[0] = [P64, P64 + 1, 2**64 - 1, 2**64 - 2**32]
+    leaves = leaves.view(np.uint8).reshape(64, 32)
+    nodes = A.merkle_nodes(leaves)
+    assert not nodes[0].any() and np.array_equal(nodes, U.merkle_nodes(leaves))
+    big = rng.integers(0, 256, size=(256, 32), dtype=np.uint8)
+    assert np.array_equal(A.merkle_nodes(big), A.merkle_nodes(big, threads=1))
+    with pytest.raises(ValueError):
+        A.merkle_nodes(big[:3])
+
+
+def _py_grind(name, seed, g, begin, max_nonces):
+    import grind_util as GU
+    for v in range(begin, min(begin + max_nonces, 2**64)):
+        d = GU.merge_with_int(None, "rp64_256", seed, v) if name == "rp64_256" else RJ.merge_with_int(seed, v)
+        if GU.qualifies(d, g):
+            return v, d
+    return None, None
+
+
+def test_rescue_ref_grind(rescue):
+    """The seeds and answers the docstrings of tests/test_gpu_grind.py (Rp64_256) and tests/test_gpu_grind_rpjive.py list."""
+    name, A, U = rescue
+
+    def K(k):
+        return hashlib.sha256(b"grind seed %d" % k).digest()
+
+    edge = b"".join(w.to_bytes(8, "little") for w in (P64, 2**64 - 1, P64 + 1, 0x0123456789ABCDEF))
+    if name == "rp64_256":   # (k, g, answer from nonce 1)
+        listed = [(2, 4, 4), (2, 8, 4), (4, 4, 12), (4, 8, 35), (1, 4, 7), (1, 8, 202), (3, 8, 66), (10, 8, 141)]
+        cases = [(K(k), g, 1, 2**64 - 1, a) for k, g, a in listed]
+        cases += [(K(1), 8, 1, 201, None), (K(1), 8, 1, 202, 202), (K(1), 8, 202, 1, 202), (K(1), 8, 203, 320, "py")]
+    else:
+        listed = [(0, 4, 11), (0, 8, 61), (2, 4, 4), (2, 8, 538), (7, 4, 13), (7, 8, 160), (10, 4, 21), (10, 8, 146), (13, 4, 6),
+                  (13, 8, 14), (22, 4, 24), (22, 8, 24), (25, 4, 71)]
+        cases = [(K(k), g, 1, 2**64 - 1, a) for k, g, a in listed]
+        cases += [(K(25), 8, 1, 300, None), (edge, 4, 1, 2**64 - 1, 3), (edge, 8, 1, 2**64 - 1, 307),
+                  (edge, 4, 2**64 - 301, 2**64 - 1, 2**64 - 289), (edge, 8, 2**64 - 301, 301, 2**64 - 205),
+                  (K(7), 8, 1, 159, None), (K(7), 8, 1, 160, 160)]
+    for seed, g, begin, max_nonces, want in cases:
+        n, d = A.grind(seed, g, begin, max_nonces)
+        if isinstance(want, int) and want - begin > 320:   # (the budget: the listed answer, and its digest from Python)
+            assert (n, d) == (want, _py_grind(name, seed, 0, want, 1)[1]), (g, begin, max_nonces)
+        else:
+            assert (n, d) == _py_grind(name, seed, g, begin, min(max_nonces, 320)), (g, begin, max_nonces)
+        if want != "py":
+            assert n == want, (g, begin, max_nonces)
+        assert A.grind(seed, g, begin, max_nonces, threads=1) == (n, d)
+    # the range ends at 2^64 - 1 whatever max_nonces says, and a factor nothing there reaches gives "none"
+    assert A.grind(edge, 40, 2**64 - 40, 2**64 - 1) == (None, None)
+    assert A.grind(edge, 0, 2**64 - 1, 2**64 - 1)[0] == 2**64 - 1

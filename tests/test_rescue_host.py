@@ -1,7 +1,9 @@
 """CPU: the Rp64_256 of csrc/rescue_dev.hpp (what the Rescue row and tree kernels run) against tests/rp64_util.py, the
 restatement of the function on Python integers, and against the reference's one literal known answer
 (tests/golden/rp64_256_kat.json).  Built with plain g++: the functions are __host__ __device__.  Both forms of the
-permutation go through every state: `P` is the one-lane-per-permutation code, `Q` the host side of the lane form."""
+permutation go through every state: `P` is the one-lane-per-permutation code, `Q` the host side of the lane form.
+`D` requests run the linear layer alone, in both forms, on the directed states of tests/rescue_edge_util.py (the closing
+addition of mds_row in each of its five cases, for every output row)."""
 import ctypes
 import json
 import os
@@ -10,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import rescue_edge_util as D
 import rp64_util as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -68,6 +71,32 @@ def _requests():
         out.append(("M", m, want))
         out.append(("L", m, want))
         out.append(("H", [x % P for x in m], want))  # merge(a, b) == hash_elements(a || b)
+    # the directed states: the linear layer alone in both forms, and the whole permutation from the state in front of the
+    # first S-box (its first linear layer meets the case)
+    out += _directed_requests()
+    for rc in D.all_pairs("rp_state")[::5]:   # case 1 of every row
+        c = D.preimage("rp64_256", D.directed_set("rp_state")[rc])
+        want = R.permute(c)
+        for op in "PQ":
+            out.append((op, c, want))
+    return out
+
+
+def _directed_requests(only=None):
+    """`D` requests: the directed states of tests/rescue_edge_util.py -- for every output row the five cases of mds_row's closing
+    addition, flagged where the 64-bit sum wraps (case 1) -- and the two extreme states, through both forms of the linear
+    layer (expected: the integer row product plus ARK1 of round 0, as residues)."""
+    row = D.PARAMS["rp64_256"]["mds_row"]
+    w = len(row)
+    ark1 = [x * 2**64 % P for x in D.PARAMS["rp64_256"]["ark1"][0]]
+    assert D.reachable("rp_state") == D.all_pairs("rp_state")
+    out = []
+    for (i, case), y in [(rc, D.directed_set("rp_state")[rc]) for rc in D.all_pairs("rp_state")] + \
+            [((0, "extra"), y) for y in D.extra_states(w)]:
+        if only is not None and case not in only:
+            continue
+        want = [(D.mds_row_value(row, y, r) + ark1[r]) % P for r in range(w)]
+        out.append(("D", [i, int(case == "wrap")] + list(y), want + want))
     return out
 
 
@@ -104,6 +133,21 @@ def test_rp64_256_under_address_and_ub_sanitizers(tmp_path):
     except subprocess.CalledProcessError:
         pytest.skip("this g++ has no sanitizer runtime")
     _run(exe, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+
+
+def test_directed_states_must_tell_the_plain_plus_copy_apart(tmp_path):
+    """The program's own guard: D requests without the wrapping states of some row end it with exit status 4."""
+    exe = _build(tmp_path)
+    reqs = _directed_requests(only=("p", "p-1", "above_p", "extra"))
+    lines = [" ".join([op] + [str(x) for x in words]) for op, words, _ in reqs]
+    res = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=120)
+    assert res.returncode == 4 and "plain-+ copy" in res.stderr
+    # the wrapping states of every row but the last: still refused, and the message names the row
+    w = len(D.PARAMS["rp64_256"]["mds_row"])
+    some = [r for r in _directed_requests(only=("wrap",)) if r[1][0] != w - 1]
+    lines = [" ".join([op] + [str(x) for x in words]) for op, words, _ in some]
+    res = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=120)
+    assert res.returncode == 4 and f"row {w - 1}" in res.stderr
 
 
 def test_header_tables_are_the_fixture_in_montgomery_form(tmp_path):
