@@ -53,12 +53,22 @@ enum wf_field { WF_FIELD_F64 = 1, WF_FIELD_F128 = 2 };
  * hash_elements with rate 4 and 1-0* padding of a partial block, and merge as ONE permutation of the two digests with the
  * Jive feed-forward sum (merge(a, b) is not hash_elements(a || b)).  Refused for it: WF_FIELD_F128 (WF_ERR_FIELD, from
  * wf_params_check, wf_hash_rows and the wf_fri_* entry points, before any launch), digest_bytes 24 (WF_ERR_DIGEST), and the
- * sharded / multi-GPU entry points (WF_ERR_ARG, as for every hasher but BLAKE3). */
-enum wf_hasher { WF_HASH_BLAKE3 = 0, WF_HASH_SHA3_256 = 1, WF_HASH_RP64_256 = 16, WF_HASH_RPJIVE64_256 = 18 };
+ * sharded / multi-GPU entry points (WF_ERR_ARG, as for every hasher but BLAKE3).
+ * GriffinJive64_256 (crypto/src/hash/griffin/griffin64_256_jive/mod.rs; id 20 -- 19 is not a hasher) is a third hasher of
+ * that kind with the same rules and the same refusals: Griffin of state width 8 (7 rounds; rate in state elements 0..4,
+ * which are also the digest), hash_elements with rate 4 and 1-0* padding of a partial block, merge as one permutation of the
+ * two digests with the Jive sum. */
+enum wf_hasher {
+    WF_HASH_BLAKE3 = 0,
+    WF_HASH_SHA3_256 = 1,
+    WF_HASH_RP64_256 = 16,
+    WF_HASH_RPJIVE64_256 = 18,
+    WF_HASH_GRIFFINJIVE64_256 = 20
+};
 
 enum wf_status {
     WF_OK = 0,
-    WF_ERR_FIELD = -10,        /* unknown field id; WF_FIELD_F128 with the Rp64_256 or RpJive64_256 hasher */
+    WF_ERR_FIELD = -10,        /* unknown field id; WF_FIELD_F128 with the Rp64_256, RpJive64_256 or GriffinJive64_256 hasher */
     WF_ERR_EXTENSION = -11,    /* ext_degree not in {1,2,3}, or 3 over f128 (f128/mod.rs:296-314) */
     WF_ERR_TRACE_LENGTH = -12, /* trace length < 8 or not a power of two (air/src/air/trace_info.rs:35) */
     WF_ERR_BLOWUP = -13,       /* blowup not a power of two in [2,128] (air/src/options.rs:19-20) */
@@ -71,7 +81,7 @@ enum wf_status {
     WF_ERR_BUSY = -20,         /* the context is inside a call of another thread (one call at a time per wf_ctx) */
     WF_ERR_HIP = -30,          /* HIP runtime failure (no device, out of memory, launch failure) */
     WF_ERR_DIGEST = -31,       /* digest_bytes is neither 32 (Blake3_256) nor 24 (Blake3_192); unknown hasher id; Sha3_256,
-                                * Rp64_256 or RpJive64_256 with digest_bytes other than 32 (wf_params, or the context's pair of setters) */
+                                * Rp64_256, RpJive64_256 or GriffinJive64_256 with digest_bytes other than 32 (wf_params, or the context's pair of setters) */
     WF_ERR_COMM = -32          /* RCCL (or caller-supplied transport) failure, librccl.so.1 not loadable */
 };
 
@@ -91,7 +101,7 @@ typedef struct wf_params {
                               * handles) are always 32-byte slots with the digest in front and zeros behind; root_out[32]
                               * is the digest zero-padded (Digest::as_bytes, crypto/src/hash/mod.rs:107-113) */
     uint32_t hasher;         /* enum wf_hasher; 0 = BLAKE3 (the field was `reserved, must be 0`: same offset and size),
-                              * 1 = Sha3_256, 16 = Rp64_256, 18 = RpJive64_256 (both: field f64 only) */
+                              * 1 = Sha3_256, 16 = Rp64_256, 18 = RpJive64_256, 20 = GriffinJive64_256 (all three: field f64 only) */
     uint8_t domain_offset[16]; /* StarkDomain::offset() as a canonical little-endian integer (7 for f64, 3 for f128) */
 } wf_params;
 
@@ -117,11 +127,11 @@ int wf_ctx_release_cached(wf_ctx *ctx);
  * functions (the reference's `H: ElementHasher` type parameter, one per Prover): 32 = Blake3_256 (default), 24 =
  * Blake3_192.  Layout rules as for wf_params::digest_bytes. */
 int wf_ctx_set_digest_bytes(wf_ctx *ctx, uint32_t digest_bytes);
-/* The other half of that hasher: WF_HASH_BLAKE3 (default), WF_HASH_SHA3_256, WF_HASH_RP64_256 or WF_HASH_RPJIVE64_256, for the same entry points (wf_hash_rows,
+/* The other half of that hasher: WF_HASH_BLAKE3 (default), WF_HASH_SHA3_256, WF_HASH_RP64_256, WF_HASH_RPJIVE64_256 or WF_HASH_GRIFFINJIVE64_256, for the same entry points (wf_hash_rows,
  * wf_merkle_build, wf_merkle_build_dev, wf_fri_layer_commit*, the layers and the remainder digest of a wf_fri_prover).
- * The pair must stay consistent: Sha3_256, Rp64_256 or RpJive64_256 on a 24-byte context, or 24 bytes on such a context, is refused with
+ * The pair must stay consistent: Sha3_256, Rp64_256, RpJive64_256 or GriffinJive64_256 on a 24-byte context, or 24 bytes on such a context, is refused with
  * WF_ERR_DIGEST and changes nothing (go through BLAKE3 / 32 bytes).  Commitments carry theirs in wf_params::hasher.
- * On an Rp64_256 or RpJive64_256 context wf_hash_rows and the wf_fri_* entry points refuse WF_FIELD_F128 with WF_ERR_FIELD. */
+ * On an Rp64_256, RpJive64_256 or GriffinJive64_256 context wf_hash_rows and the wf_fri_* entry points refuse WF_FIELD_F128 with WF_ERR_FIELD. */
 int wf_ctx_set_hasher(wf_ctx *ctx, uint32_t hasher);
 /* Diagnostic (needs no device): the digit passes the commitment path uses for a transform of 2^log2_n rows over
  * n_segments segments (a segment = 8 f64 / 4 f128 base columns); returns the number of passes (<= 4), digits_out[i] =
@@ -585,7 +595,7 @@ int wf_merkle_build(wf_ctx *ctx, const uint8_t *leaves, size_t n_leaves, uint8_t
  * seed after reseed_with_int.  found_out[i] = 1, or 0 with nonce 0 and a zero slot when the range holds no such nonce.
  * The reference starts at 1 and allows grinding_factor <= 32 (air/src/options.rs:22).
  * The hasher is the context's pair (wf_ctx_set_hasher / wf_ctx_set_digest_bytes), as for the FRI functions; seed words of
- * an Rp64_256 or RpJive64_256 context are read as BaseElement::new reads them.  The range ends at 2^64 - 1 at the latest (it never wraps).
+ * an Rp64_256, RpJive64_256 or GriffinJive64_256 context are read as BaseElement::new reads them.  The range ends at 2^64 - 1 at the latest (it never wraps).
  * The search runs on the device in windows that double from a first one (2^16 or 2^20 nonces, by hasher) up to a
  * per-hasher cap of a few milliseconds, the host looking at the result between two windows: the call is host-blocking (it returns with the answer) and cannot be captured into a graph.
  * It is queued on the context's stream behind whatever the context was given before.

@@ -254,6 +254,9 @@ struct Rp64_256 {  // f64 matrices only; a digest is ElementDigest::as_bytes (fo
 struct RpJive64_256 {  // the same rules as Rp64_256; merge is one width-8 permutation with the Jive sum
     static constexpr uint32_t ID = WF_HASH_RPJIVE64_256;
 };
+struct GriffinJive64_256 {  // the same rules as Rp64_256; Griffin of width 8, merge is one permutation with the Jive sum
+    static constexpr uint32_t ID = WF_HASH_GRIFFINJIVE64_256;
+};
 
 class Prover {
   public:

@@ -20,7 +20,7 @@ pub struct WfParams {
     pub n_traces: u32,
     pub digest_bytes: u32,
     /// `enum wf_hasher`: 0 = BLAKE3, 1 = Sha3_256 (32-byte digests only), 16 = Rp64_256 (f64 only, 32-byte digests:
-    /// four canonical little-endian u64, `ElementDigest::as_bytes`), 18 = RpJive64_256 (the same rules as Rp64_256)
+    /// four canonical little-endian u64, `ElementDigest::as_bytes`), 18 = RpJive64_256, 20 = GriffinJive64_256 (the same rules as Rp64_256)
     pub hasher: u32,
     pub domain_offset: [u8; 16],
 }
@@ -159,7 +159,7 @@ extern "C" {
     ) -> c_int;
     pub fn wf_ctx_set_digest_bytes(ctx: *mut WfCtx, digest_bytes: u32) -> c_int;
     /// The other half of the context's hasher (FRI, `wf_hash_rows`, `wf_merkle_build`): 0 = BLAKE3, 1 = Sha3_256, 16 = Rp64_256,
-    /// 18 = RpJive64_256.
+    /// 18 = RpJive64_256, 20 = GriffinJive64_256.
     pub fn wf_ctx_set_hasher(ctx: *mut WfCtx, hasher: u32) -> c_int;
     /// A stream of proofs: returns once the columns are on their way; `wf_commitment_wait` (or `wf_commitment_root`) completes it.
     pub fn wf_trace_commit_resident_async(

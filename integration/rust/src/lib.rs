@@ -111,6 +111,19 @@ impl WfHasher for crypto::hashers::RpJive64_256 {
     }
 }
 
+/// `GriffinJive64_256` (`crypto/src/hash/griffin/griffin64_256_jive/mod.rs`; `WF_HASH_GRIFFINJIVE64_256` = 20): an element
+/// digest with the same rules as `Rp64_256`.
+impl WfHasher for crypto::hashers::GriffinJive64_256 {
+    const DIGEST_BYTES: u32 = 32;
+    const HASHER: u32 = 20;
+    fn digests_from_library(digests: &mut [Self::Digest]) {
+        for d in digests.iter_mut() {
+            let bytes: [u8; 32] = unsafe { core::ptr::read(d as *const Self::Digest as *const [u8; 32]) };
+            *d = <Self::Digest as Deserializable>::read_from_bytes(&bytes).expect("digest");
+        }
+    }
+}
+
 // CONTEXT
 // ================================================================================================
 

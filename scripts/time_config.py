@@ -1,13 +1,13 @@
 """Times the device-buffer form of the trace commitment for an arbitrary configuration (bring-up / tuning aid).
     python scripts/time_config.py <field 1|2> <ext> <log2 R> <log2 blowup> <n_cols> <n_traces> [hasher id] [--hasher NAME|id]
-(hasher: 0 / blake3 = BLAKE3, 1 / sha3 = Sha3_256, 16 / rp64 = Rp64_256, 18 / rpjive = RpJive64_256; the profile marks split the time into the
+(hasher: 0 / blake3 = BLAKE3, 1 / sha3 = Sha3_256, 16 / rp64 = Rp64_256, 18 / rpjive = RpJive64_256, 20 / griffin = GriffinJive64_256; the profile marks split the time into the
 transform, "hash_rows" and "merkle")"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import starkpack_winterfell_amd.capi as capi
 
-HASHERS = {"blake3": capi.BLAKE3, "sha3": capi.SHA3_256, "rp64": capi.RP64_256, "rpjive": capi.RPJIVE64_256}
+HASHERS = {"blake3": capi.BLAKE3, "sha3": capi.SHA3_256, "rp64": capi.RP64_256, "rpjive": capi.RPJIVE64_256, "griffin": capi.GRIFFINJIVE64_256}
 argv = sys.argv[1:]
 hasher = capi.BLAKE3
 if "--hasher" in argv:

@@ -5,18 +5,18 @@
      second = range / device time of the launches, and each window's size and time -- what the window cap is set from.
   3. floor: a call at factor 0 (one window, first nonce).
   4. the CPU's merge_with_int on one thread (the oracle's BLAKE3 through ctypes, call overhead included; hashlib's SHA3).
-Compare the rates with the register-only loops of scripts/merkle_bench.hip, keccak_bench.hip, rescue_bench.hip and rescue_jive_bench.hip run in the
+Compare the rates with the register-only loops of scripts/merkle_bench.hip, keccak_bench.hip, rescue_bench.hip, rescue_jive_bench.hip and griffin_bench.hip run in the
 same session.
-    python scripts/time_grind.py [hasher ...]     hashers: blake3_256 blake3_192 sha3_256 rp64_256 rpjive64_256 (default: all)"""
+    python scripts/time_grind.py [hasher ...]     hashers: blake3_256 blake3_192 sha3_256 rp64_256 rpjive64_256 griffin (default: all)"""
 import hashlib, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import starkpack_winterfell_amd.capi as capi
 
 HASHERS = {"blake3_256": (capi.BLAKE3, 32), "blake3_192": (capi.BLAKE3, 24), "sha3_256": (capi.SHA3_256, 32),
-           "rp64_256": (capi.RP64_256, 32), "rpjive64_256": (capi.RPJIVE64_256, 32)}
-FACTORS = {"rp64_256": (12, 16, 20), "rpjive64_256": (12, 16, 20)}
-RATE_RANGE_LOG2 = {"blake3_256": 31, "blake3_192": 31, "sha3_256": 29, "rp64_256": 25, "rpjive64_256": 25}
+           "rp64_256": (capi.RP64_256, 32), "rpjive64_256": (capi.RPJIVE64_256, 32), "griffin": (capi.GRIFFINJIVE64_256, 32)}
+FACTORS = {"rp64_256": (12, 16, 20), "rpjive64_256": (12, 16, 20), "griffin": (12, 16, 20)}
+RATE_RANGE_LOG2 = {"blake3_256": 31, "blake3_192": 31, "sha3_256": 29, "rp64_256": 25, "rpjive64_256": 25, "griffin": 27}
 WARMUP, REPEATS = 2, 5
 
 

@@ -15,7 +15,7 @@ import numpy as np
 from .build import lib_path
 
 F64, F128 = 1, 2
-BLAKE3, SHA3_256, RP64_256, RPJIVE64_256 = 0, 1, 16, 18  # enum wf_hasher (0..15 byte-digest hashers, element-digest hashers from 16)
+BLAKE3, SHA3_256, RP64_256, RPJIVE64_256, GRIFFINJIVE64_256 = 0, 1, 16, 18, 20  # enum wf_hasher (0..15 byte-digest hashers, element-digest hashers from 16)
 ELEM_WORDS = {F64: 1, F128: 2}
 
 SYMBOLS = [
@@ -81,7 +81,8 @@ class Query(C.Structure):
 def make_params(field, ext_degree, log2_trace_len, log2_blowup, n_cols, n_traces=1, offset=None, digest_bytes=32, hasher=0) -> Params:
     """digest_bytes: 32 = Blake3_256, 24 = Blake3_192 (host arrays of digests are then 24 bytes per entry); hasher: BLAKE3 (0)
     SHA3_256 (1: Sha3_256, 32-byte digests only), RP64_256 (16: Rescue Prime over f64, field F64 and 32-byte digests only) or
-    RPJIVE64_256 (18: Rescue Prime of width 8 with Jive compression, the same restrictions)."""
+    RPJIVE64_256 (18: Rescue Prime of width 8 with Jive compression, the same restrictions) or GRIFFINJIVE64_256 (20: Griffin of
+    width 8 with Jive compression, the same restrictions)."""
     if offset is None:
         offset = 7 if field == F64 else 3  # ProofOptions::domain_offset = B::GENERATOR, air/src/options.rs:199-201
     p = Params(field, ext_degree, log2_trace_len, log2_blowup, n_cols, n_traces, digest_bytes, hasher)
@@ -300,8 +301,8 @@ class Context:
         self.digest_bytes = n
 
     def set_hasher(self, hasher: int):
-        """wf_ctx_set_hasher: BLAKE3 (default), SHA3_256, RP64_256 or RPJIVE64_256 for hash_rows / merkle_build / the FRI entry points (an
-        inconsistent pair -- Sha3_256, Rp64_256 or RpJive64_256 with 24-byte digests -- raises WfError -31 and changes nothing)."""
+        """wf_ctx_set_hasher: BLAKE3 (default), SHA3_256, RP64_256, RPJIVE64_256 or GRIFFINJIVE64_256 for hash_rows / merkle_build / the FRI entry points (an
+        inconsistent pair -- Sha3_256, Rp64_256, RpJive64_256 or GriffinJive64_256 with 24-byte digests -- raises WfError -31 and changes nothing)."""
         _check(load().wf_ctx_set_hasher(self._h, hasher))
         self.hasher = hasher
 

@@ -318,13 +318,14 @@ static const char *hasher_name(uint32_t hasher) {
            : hasher == WF_HASH_SHA3_256      ? "Sha3_256"
            : hasher == WF_HASH_RP64_256      ? "Rp64_256"
            : hasher == WF_HASH_RPJIVE64_256 ? "RpJive64_256"
+           : hasher == WF_HASH_GRIFFINJIVE64_256 ? "GriffinJive64_256"
                                              : nullptr;
 }
 
 // a known hasher id, and a digest size that hasher has (BLAKE3: 32 or 24, the others 32)
 int check_hasher_pair(uint32_t hasher, uint32_t digest_bytes) {
     if (!hasher_name(hasher))
-        return fail(WF_ERR_DIGEST, "unknown hasher id %u (0 = BLAKE3, 1 = Sha3_256, 16 = Rp64_256, 18 = RpJive64_256)", hasher);
+        return fail(WF_ERR_DIGEST, "unknown hasher id %u (0 = BLAKE3, 1 = Sha3_256, 16 = Rp64_256, 18 = RpJive64_256, 20 = GriffinJive64_256)", hasher);
     if (hasher != WF_HASH_BLAKE3 && digest_bytes != 32)
         return fail(WF_ERR_DIGEST, "%s has 32-byte digests, got digest_bytes %u", hasher_name(hasher), digest_bytes);
     return 0;
@@ -332,7 +333,7 @@ int check_hasher_pair(uint32_t hasher, uint32_t digest_bytes) {
 
 // an element-digest hasher hashes elements of its own field only
 int check_hasher_field(uint32_t hasher, uint32_t field) {
-    if ((hasher == WF_HASH_RP64_256 || hasher == WF_HASH_RPJIVE64_256) && field != WF_FIELD_F64)
+    if ((hasher == WF_HASH_RP64_256 || hasher == WF_HASH_RPJIVE64_256 || hasher == WF_HASH_GRIFFINJIVE64_256) && field != WF_FIELD_F64)
         return fail(WF_ERR_FIELD, "%s hashes elements of the f64 field only (field id %u)", hasher_name(hasher), field);
     return 0;
 }

@@ -1,7 +1,7 @@
 // libwf_field_probe.so -- test helper, NOT part of the product ABI (nothing in include/wf_lde.h, nothing in libwf_lde.so
 // uses it; same footing as libwf_yardstick.so): the field primitives of field.hpp, the extension products of
-// fri_kernels.hpp, the Rescue S-boxes of rescue_dev.hpp and the MDS rows of both Rescue hashers (one-lane form, every row of
-// one state, no round constants) as the DEVICE compiler emits them, one element per thread, so
+// fri_kernels.hpp, the Rescue S-boxes of rescue_dev.hpp, the MDS rows of both Rescue hashers (one-lane form, every row of
+// one state, no round constants) and the linear form and non-linear layer of griffin_dev.hpp as the DEVICE compiler emits them, one element per thread, so
 // that tests/test_gpu_field_probe.py can feed the 32-bit carry and borrow chains the operands that make their rare
 // branches fire and compare every result with integer arithmetic.
 //
@@ -14,6 +14,7 @@
 #include "fri_kernels.hpp"
 #include "rescue_dev.hpp"
 #include "rescue_jive_dev.hpp"
+#include "griffin_dev.hpp"
 
 using namespace wf;
 
@@ -37,8 +38,11 @@ enum Op {
     OP_RP_INV_SBOX = 14,
     OP_RP_MDS_ROWS = 15,   // 12 words in, 12 out: out[i] = rp::mds_row(i) of the state
     OP_RPJ_MDS_ROWS = 16,  // 8 words in, 8 out: out[i] = rpj::mds_row(i) of the state
-    OP_COUNT = 17
+    OP_COUNT = 17,         // ops 0 .. 16 are contiguous; 17 .. 31 are not ops
+    OP_GFJ_LINEAR = 32,    // 4 words in (i = 2..7, z0, z1, t as raw residues), 1 out: gfj::linear(i, z0, z1, t); another i gives 0
+    OP_GFJ_NONLINEAR = 33  // 8 words in, 8 out: gfj::nonlinear of the state
 };
+constexpr bool is_op(int op) { return (op >= 0 && op < OP_COUNT) || op == OP_GFJ_LINEAR || op == OP_GFJ_NONLINEAR; }
 
 // mul_pow2<1..63> | div_pow2<1..32> | neg_div_pow2<1..32> | neg_mul_pow2<33..63> | mul_pow2_192<0..191>
 constexpr int SHIFT_MUL_AT = 0, SHIFT_DIV_AT = 63, SHIFT_NEG_DIV_AT = 95, SHIFT_NEG_MUL_AT = 127, SHIFT_192_AT = 158;
@@ -88,6 +92,8 @@ constexpr Shape shape_of(int op) {
         case OP_EXT_MUL_F128_2: return {4, 4, 4};
         case OP_RP_MDS_ROWS: return {rp::STATE, 0, rp::STATE};
         case OP_RPJ_MDS_ROWS: return {rpj::STATE, 0, rpj::STATE};
+        case OP_GFJ_LINEAR: return {4, 0, 1};
+        case OP_GFJ_NONLINEAR: return {gfj::STATE, 0, gfj::STATE};
         default: return {0, 0, 0};
     }
 }
@@ -142,6 +148,25 @@ __global__ void __launch_bounds__(256) k_probe(const uint64_t *__restrict__ a, c
         for (int j = 0; j < rpj::STATE; j++) s[j] = pa[j];
 #pragma unroll
         for (int i = 0; i < rpj::STATE; i++) po[i] = rpj::mds_row((uint32_t)i, [&](uint32_t j) { return s[j]; });
+    } else if constexpr (OP == OP_GFJ_LINEAR) {
+        uint64_t l = 0;  // the product calls linear with a compile-time i: so does every arm here
+        switch (pa[0]) {
+            case 2: l = gfj::linear(2, pa[1], pa[2], pa[3]); break;
+            case 3: l = gfj::linear(3, pa[1], pa[2], pa[3]); break;
+            case 4: l = gfj::linear(4, pa[1], pa[2], pa[3]); break;
+            case 5: l = gfj::linear(5, pa[1], pa[2], pa[3]); break;
+            case 6: l = gfj::linear(6, pa[1], pa[2], pa[3]); break;
+            case 7: l = gfj::linear(7, pa[1], pa[2], pa[3]); break;
+            default: break;
+        }
+        po[0] = l;
+    } else if constexpr (OP == OP_GFJ_NONLINEAR) {
+        uint64_t s[gfj::STATE];
+#pragma unroll
+        for (int j = 0; j < gfj::STATE; j++) s[j] = pa[j];
+        gfj::nonlinear(s);
+#pragma unroll
+        for (int j = 0; j < gfj::STATE; j++) po[j] = s[j];
     }
 }
 
@@ -154,6 +179,10 @@ void launch_ops(int op, const uint64_t *a, const uint64_t *b, uint64_t *out, siz
         } else {
             launch_ops<OP + 1>(op, a, b, out, n, st);
         }
+    } else {  // the ops behind the gap
+        const unsigned blocks = (unsigned)((n + 255) / 256);
+        if (op == OP_GFJ_LINEAR) k_probe<OP_GFJ_LINEAR><<<blocks, 256, 0, st>>>(a, b, out, n);
+        else if (op == OP_GFJ_NONLINEAR) k_probe<OP_GFJ_NONLINEAR><<<blocks, 256, 0, st>>>(a, b, out, n);
     }
 }
 
@@ -172,7 +201,7 @@ struct Buffers {
 
 // words per element of (a, b, out) for `op`; 0 for an unknown op
 extern "C" int wf_field_probe_words(int op, int *a_words, int *b_words, int *out_words) {
-    if (op < 0 || op >= OP_COUNT) return 0;
+    if (!is_op(op)) return 0;
     const Shape s = shape_of(op);
     *a_words = s.a;
     *b_words = s.b;
@@ -186,7 +215,7 @@ extern "C" int wf_field_probe_words(int op, int *a_words, int *b_words, int *out
 // the op's words per element (a test helper has no business taking more of a shared device).  Returns a hipError_t.
 extern "C" int wf_field_probe(int device, int op, const void *a, const void *b, void *out, size_t n, size_t out_capacity) {
     constexpr size_t MAX_BYTES = (size_t)64 << 20;
-    if (op < 0 || op >= OP_COUNT || out_capacity < n) return (int)hipErrorInvalidValue;
+    if (!is_op(op) || out_capacity < n) return (int)hipErrorInvalidValue;
     if (n == 0) return (int)hipSuccess;
     const Shape s = shape_of(op);
     if (!a || !out || (s.b && !b)) return (int)hipErrorInvalidValue;

@@ -93,6 +93,7 @@ extern "C" int wf_grind_seeds(wf_ctx *ctx, const uint8_t *seeds, size_t n_seeds,
     HIP_TRY(hipMemcpyAsync(dev, pin, L.nonces, hipMemcpyHostToDevice, st));
     GrindPlan plan = ctx->hasher == WF_HASH_RP64_256        ? GRIND_PLAN_RP64
                      : ctx->hasher == WF_HASH_RPJIVE64_256 ? GRIND_PLAN_RPJIVE
+                     : ctx->hasher == WF_HASH_GRIFFINJIVE64_256 ? GRIND_PLAN_GRIFFIN
                      : ctx->hasher == WF_HASH_SHA3_256     ? GRIND_PLAN_SHA3
                                                            : GRIND_PLAN_BLAKE3;
     if (ctx->tune.grind_window_cap_log2) plan.cap_log2 = ctx->tune.grind_window_cap_log2;
@@ -103,6 +104,8 @@ extern "C" int wf_grind_seeds(wf_ctx *ctx, const uint8_t *seeds, size_t n_seeds,
         rc = grind_run<GrindRp64>(ctx, st, dev, pin, L, n, grinding_factor, nonce_begin, max_nonces, plan);
     else if (ctx->hasher == WF_HASH_RPJIVE64_256)
         rc = grind_run<GrindRpJive>(ctx, st, dev, pin, L, n, grinding_factor, nonce_begin, max_nonces, plan);
+    else if (ctx->hasher == WF_HASH_GRIFFINJIVE64_256)
+        rc = grind_run<GrindGriffin>(ctx, st, dev, pin, L, n, grinding_factor, nonce_begin, max_nonces, plan);
     else if (ctx->hasher == WF_HASH_SHA3_256)
         rc = grind_run<GrindSha3>(ctx, st, dev, pin, L, n, grinding_factor, nonce_begin, max_nonces, plan);
     else if (ctx->digest_bytes == 24)

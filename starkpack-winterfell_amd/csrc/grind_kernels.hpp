@@ -15,6 +15,7 @@
 #include "keccak_dev.hpp"
 #include "rescue_dev.hpp"
 #include "rescue_jive_dev.hpp"
+#include "griffin_dev.hpp"
 
 namespace wf {
 
@@ -106,6 +107,22 @@ struct GrindRpJive {
     }
     static __device__ __forceinline__ void digest(const Seed &s, uint64_t nonce, uint64_t (&out)[4]) {
         rpj::merge_with_int_mont(s.w, nonce, out);
+    }
+};
+
+// GriffinJive64_256 (gfj::permute, one lane per permutation): the seed handling of GrindRp64; merge_with_int is the Jive
+// compression of seed || nonce (gfj::merge_with_int_mont).
+struct GrindGriffin {
+    typedef GrindRp64::Seed Seed;
+    static __device__ __forceinline__ void prepare(const uint64_t *slot, Seed &s) { GrindRp64::prepare(slot, s); }
+    static __device__ __forceinline__ void wave_uniform(Seed &s) { GrindRp64::wave_uniform(s); }
+    static __device__ __forceinline__ uint32_t head32(const Seed &s, uint64_t nonce) {
+        uint64_t d[4];
+        gfj::merge_with_int_mont(s.w, nonce, d);
+        return (uint32_t)d[0];
+    }
+    static __device__ __forceinline__ void digest(const Seed &s, uint64_t nonce, uint64_t (&out)[4]) {
+        gfj::merge_with_int_mont(s.w, nonce, out);
     }
 };
 

@@ -34,6 +34,12 @@ constexpr GrindPlan GRIND_PLAN_RP64 = {16, 20, 1};
 // the register-only loop of the width-8 permutation; 2^21 would be 3.4 ms).  The same three numbers as Rp64_256 come out; one
 // nonce per lane is taken over from it and was not measured again.
 constexpr GrindPlan GRIND_PLAN_RPJIVE = {16, 20, 1};
+// GriffinJive64_256 (scripts/time_grind.py griffin, profiles/griffin_grind.txt): one permutation's latency is 0.044 ms, which
+// 2^16 nonces still cost (0.049 ms; 2^17: 0.059, 2^18: 0.096, 2^19: 0.169, 2^20: 0.315, 2^21: 0.611): that launch is the
+// smallest there is, 2.5 looks of the host.  2^22 are 1.19 ms (3.48 G nonces/s, 103 % of the register-only loop of the
+// permutation); 2^23 would be 2.4 ms and was not timed.  One nonce per lane: the same library with 8 per lane gives 1.31 ms for
+// 2^22 (3.18 G nonces/s) in the same session, as Rp64_256 found.
+constexpr GrindPlan GRIND_PLAN_GRIFFIN = {16, 22, 1};
 
 struct GrindWindow {
     uint64_t base, count;  // nonces base .. base + count - 1; count == 0: the range is spent

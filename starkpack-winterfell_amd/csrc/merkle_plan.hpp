@@ -36,6 +36,15 @@ constexpr MerklePlan MERKLE_PLAN_RP64 = {false, 16, 0, 7, 64, 1024};
 // from 2^16 / 2^17 / 2^18 / 2^19 parents up, 2^18 leaves 1.170 / 1.086 ms from 2^16 / 2^17; two earlier sessions order them
 // the same way (14.49 / 14.26 / 14.46 / 14.77; 1.165 / 1.090 and 1.192 / 1.105).
 constexpr MerklePlan MERKLE_PLAN_RPJIVE = {false, 17, 0, 8, 128, 1024};
+// GriffinJive64_256: one lane per parent throughout (gfj::merge has no lane-split form), so Sha3_256's shape -- the generic
+// LDS sub-tree kernel, 9 levels per launch -- with the switch one level up.  Measured (docs/EXPERIMENTS.md
+// "GriffinJive64_256", scripts/griffin_bench.hip, profiles/griffin_bench.txt): a level of up to 2^15 parents costs one
+// permutation's latency in either kernel (0.049 ms; 2^16: 0.052, 2^17: 0.065, 2^18: 0.107), so the switch moves little.  Whole
+// trees, ms, three rounds each, with k_merkle_level from 2^14 / 2^15 / 2^16 / 2^17 / 2^18 parents up: 2^23 leaves
+// 3.514 3.508 3.562 / 3.519 3.510 3.517 / 3.495 3.493 3.503 / 3.478 3.516 3.487 / 3.585 3.572 3.617; 2^18 leaves
+// 0.970 0.958 0.939 / 0.951 0.952 0.948 / 0.947 0.936 0.934 / 0.943 0.949 0.945.  2^16 is the only value that is first or
+// second in all six columns.  (From 2^10 up the small tree gains 5 %, 0.874 .. 0.909, and the large one loses 5 %, 3.66 .. 3.72.)
+constexpr MerklePlan MERKLE_PLAN_GRIFFIN = {false, 16, 0, 9, 256, 256};
 
 enum MerkleLaunch : uint32_t { MERKLE_LEVEL2, MERKLE_LEVEL, MERKLE_SUBTREE };
 

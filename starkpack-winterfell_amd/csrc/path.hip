@@ -9,6 +9,7 @@
 #include "merkle_plan.hpp"
 #include "rescue_kernels.hpp"
 #include "rescue_jive_kernels.hpp"
+#include "griffin_dev.hpp"
 #include "seg_kernels.hpp"
 #include "col_kernels.hpp"
 #include "fri_kernels.hpp"
@@ -703,12 +704,15 @@ static int run_hash_rows(wf_ctx *ctx, hipStream_t st, const void *lde, uint64_t 
     if (hasher != WF_HASH_BLAKE3) {  // the sponge hashers: one lane per row absorbs the whole row, whatever its length
         if (hasher == WF_HASH_RP64_256 && F::FIELD_ID != 1) return fail(WF_ERR_FIELD, "Rp64_256 hashes elements of the f64 field only");
         if (hasher == WF_HASH_RPJIVE64_256 && F::FIELD_ID != 1) return fail(WF_ERR_FIELD, "RpJive64_256 hashes elements of the f64 field only");
+        if (hasher == WF_HASH_GRIFFINJIVE64_256 && F::FIELD_ID != 1) return fail(WF_ERR_FIELD, "GriffinJive64_256 hashes elements of the f64 field only");
         if (grid > 0x7FFFFFFFull) return fail(WF_ERR_ARG, "too many rows for one launch");
         if (hasher == WF_HASH_SHA3_256)
             hipLaunchKernelGGL((k_hash_rows_sponge<F, k3::Absorb>), dim3((uint32_t)grid), dim3(threads), 0, st, h);
         else if constexpr (F::FIELD_ID == 1) {  // (the sponge takes the stored (Montgomery) elements as they are)
             if (hasher == WF_HASH_RPJIVE64_256)
                 hipLaunchKernelGGL((k_hash_rows_sponge<F, rpj::Absorb>), dim3((uint32_t)grid), dim3(threads), 0, st, h);
+            else if (hasher == WF_HASH_GRIFFINJIVE64_256)
+                hipLaunchKernelGGL((k_hash_rows_sponge<F, gfj::Absorb>), dim3((uint32_t)grid), dim3(threads), 0, st, h);
             else
                 hipLaunchKernelGGL((k_hash_rows_sponge<F, rp::Absorb>), dim3((uint32_t)grid), dim3(threads), 0, st, h);
         }
@@ -789,6 +793,7 @@ static int run_merkle(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t 
     if (hasher == WF_HASH_SHA3_256) return run_merkle_plan<k3::Merge, MERKLE_PLAN_SHA3>(ctx, st, leaves, n_leaves, nodes);
     if (hasher == WF_HASH_RP64_256) return run_merkle_plan<rp::Merge, MERKLE_PLAN_RP64>(ctx, st, leaves, n_leaves, nodes);
     if (hasher == WF_HASH_RPJIVE64_256) return run_merkle_plan<rpj::Merge, MERKLE_PLAN_RPJIVE>(ctx, st, leaves, n_leaves, nodes);
+    if (hasher == WF_HASH_GRIFFINJIVE64_256) return run_merkle_plan<gfj::Merge, MERKLE_PLAN_GRIFFIN>(ctx, st, leaves, n_leaves, nodes);
     return digest_bytes == 24 ? run_merkle_plan<b3::Merge<6>, MERKLE_PLAN_BLAKE3>(ctx, st, leaves, n_leaves, nodes)
                               : run_merkle_plan<b3::Merge<8>, MERKLE_PLAN_BLAKE3>(ctx, st, leaves, n_leaves, nodes);
 }

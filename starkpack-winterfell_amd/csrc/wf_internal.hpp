@@ -210,7 +210,7 @@ int upload_columns(wf_ctx *ctx, void *dst, const void *const *cols, size_t n, si
 int download_columns(wf_ctx *ctx, void *const *cols, const void *src, size_t n, size_t colb, hipStream_t st);
 int check_params(const wf_params *p, bool constraint);
 int check_hasher_pair(uint32_t hasher, uint32_t digest_bytes);  // WF_ERR_DIGEST: unknown id, or a digest size the hasher lacks
-int check_hasher_field(uint32_t hasher, uint32_t field);        // WF_ERR_FIELD: Rp64_256 or RpJive64_256 with a field other than f64
+int check_hasher_field(uint32_t hasher, uint32_t field);        // WF_ERR_FIELD: an element-digest hasher (ids from 16) with a field other than f64
 int check_blake3_only(const wf_params *p, const char *what);  // the multi-GPU entry points: WF_ERR_ARG for another hasher
 
 // ------------------------------------------------------------------------------------------------- comm.hip
