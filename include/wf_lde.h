@@ -392,6 +392,82 @@ typedef struct wf_evaluation_table {
 } wf_evaluation_table;
 int wf_constraint_commit_from_tables(wf_ctx *ctx, const wf_params *p, const wf_evaluation_table *tables, size_t n_tables,
                                      size_t ce_domain_size, const void *final_coeff, void *const *polys_out, wf_commitment **out);
+
+/* ---- constraint programs: the constraint evaluation table from the RESIDENT trace LDE ---------------------------------
+ * ConstraintEvaluator::evaluate (prover/src/constraints/evaluator.rs:74-241) for the main trace segment
+ * (evaluate_fragment_main, :140-190) without the extended trace visiting the host.  Air::evaluate_transition and the boundary
+ * constraints are polynomial expressions, the same for every row, so the caller (or a tracer that runs evaluate_transition on
+ * a symbolic element type) hands them over as a straight-line PROGRAM of field additions, subtractions and products; one
+ * generic kernel runs it for every step of the constraint evaluation domain.  Nothing in the library is AIR-specific.
+ *
+ * Row mapping.  n = the commitment's LDE row count, ce = trace length << log2_ce_blowup.  For step in 0 .. ce:
+ *   lde_step = step << (log2_blowup - log2_ce_blowup); CUR c = element c of LDE row lde_step of matrix trace_index;
+ *   NEXT c = element c of row (lde_step + lde_blowup) mod n (TraceLde::read_main_trace_frame_into, prover/src/trace/trace_lde.rs:78-93);
+ *   rows are as wide as wf_commitment_read_lde reports, c < n_cols of the commitment.
+ * Other operand sources.  X = offset * g_ce^step (StarkDomain::get_ce_x_at, prover/src/domain.rs:124-131).  CONST k = base
+ *   constant k, ECONST k = constant k of E.  TABLE t at step = values[(step - shift) mod 2^log2_len], shift < 2^log2_len <= ce:
+ *   PeriodicValueTable::get_row (prover/src/constraints/periodic_table.rs:84-91; shift 0) and LargePolyConstraint::evaluate
+ *   (prover/src/constraints/boundary.rs:447-460; shift = step_offset); a SmallPolyConstraint is X and constants.  The index
+ *   field of an X operand is ignored.
+ * Typing.  A source is of base type, or of type E (only ECONST); a register has ONE type for the whole program, fixed by its
+ *   first write.  An op whose operands are both base is a base-field op and writes a base register; otherwise it is an E op: a
+ *   base operand is embedded (mul_base for MUL) and it writes an E register.  With ext_degree == 1 the two types coincide.
+ *   out_regs[j] may be of either type (a base value is embedded when stored).  Every result is the field value, i.e. what the
+ *   reference computes; the reference evaluates main transition constraints in the base field and merges them with
+ *   coef.mul_base (evaluator.rs:266-275) -- a program that keeps that order keeps its products cheap.
+ * Refused, before anything is launched: WF_ERR_ARG for null pointers, non-zero reserved fields, an unknown op or source (source
+ *   kinds from 7 on are reserved for the auxiliary frame), counts outside the ranges below, a dst / register / constant / table /
+ *   column index out of range, a register read before it is written or written with a second type, an out_regs entry never
+ *   written, a constant or table value that is not a valid field element, shift >= 2^log2_len or 2^log2_len > ce,
+ *   trace_index >= n_traces, registers that take more than 64 (f64) / 32 (f128) base elements (a base register counts once, an
+ *   E register ext_degree times: the registers live in the local memory of a compute unit) or a frame that does not fit next to
+ *   them (320 f64 / 160 f128 base elements for frame columns, x and registers together), a commitment whose ext_degree is not 1
+ *   or that holds no rows; WF_ERR_EXTENSION for ext_degree outside {1, 2, 3} or 3 over f128; WF_ERR_BLOWUP for
+ *   log2_ce_blowup == 0 or > log2_blowup.
+ * Ordering and lifetime.  The call is queued on the context's stream behind the commitment's kernels (a handle from
+ *   wf_trace_commit_resident_async is valid input) and returns without waiting; the program, its constants and its tables have
+ *   been copied when it returns (into pinned memory of the handle, from where the upload is queued).  Only wf_evaluations_read
+ *   blocks; wf_evaluations_destroy waits for that upload -- not for the kernel -- before it frees the pinned copy.  The handle owns n_out device columns of ce elements of E
+ *   and follows the commitments' rules for a context that is destroyed first. */
+enum wf_cprog_op { WF_CP_ADD = 1, WF_CP_SUB = 2, WF_CP_MUL = 3 };
+enum wf_cprog_src { WF_CP_REG = 0, WF_CP_CUR = 1, WF_CP_NEXT = 2, WF_CP_CONST = 3, WF_CP_ECONST = 4, WF_CP_TABLE = 5, WF_CP_X = 6 };
+typedef struct wf_cprog_instr { /* dst = a op b; 12 bytes */
+    uint8_t op, a_src, b_src, reserved0;
+    uint16_t dst, a, b, reserved1;
+} wf_cprog_instr;
+typedef struct wf_cprog_table {
+    const void *values; /* 2^log2_len base-field elements, host memory */
+    uint32_t log2_len;
+    uint32_t reserved;
+    uint64_t shift;
+} wf_cprog_table;
+typedef struct wf_cprog {
+    const wf_cprog_instr *instrs;
+    uint32_t n_instrs; /* 1 .. 4096 */
+    uint32_t n_regs;   /* 1 .. 64 */
+    const void *consts; /* base-field elements, memory representation */
+    uint32_t n_consts;
+    const void *econsts; /* elements of E (ext_degree coordinates each) */
+    uint32_t n_econsts;
+    const wf_cprog_table *tables;
+    uint32_t n_tables;
+    const uint16_t *out_regs; /* register holding evaluation column j */
+    uint32_t n_out;           /* 1 .. 32 */
+} wf_cprog;
+typedef struct wf_evaluations wf_evaluations;
+int wf_constraint_evaluate(const wf_commitment *trace, uint32_t trace_index, const wf_cprog *prog, uint32_t ext_degree,
+                           uint32_t log2_ce_blowup, wf_evaluations **out);
+int wf_evaluations_info(const wf_evaluations *e, uint32_t *n_columns, uint64_t *ce_domain_size, uint32_t *ext_degree);
+/* column `column` as ce_domain_size elements of E into host memory; waits for the evaluation */
+int wf_evaluations_read(const wf_evaluations *e, uint32_t column, void *out);
+void wf_evaluations_destroy(wf_evaluations *e);
+/* wf_constraint_commit_from_tables with the tables' columns already in device memory: tables[i] is the evaluation table of
+ * packed trace i, divisors[i] its tables[i]->n_columns divisors, ce_domain_size the handles'.  Root, rows and polynomials are
+ * those of the host-table call fed the wf_evaluations_read copies, byte for byte; the columns are read in place.  Handles of
+ * another context, of different sizes, or whose field / extension degree differ from p's: WF_ERR_ARG. */
+int wf_constraint_commit_from_device_tables(wf_ctx *ctx, const wf_params *p, const wf_evaluations *const *tables,
+                                            const wf_divisor *const *divisors, size_t n_tables, const void *final_coeff,
+                                            void *const *polys_out, wf_commitment **out);
 void wf_commitment_destroy(wf_commitment *c);
 /* MerkleTree::root (merkle/mod.rs:167) */
 int wf_commitment_root(const wf_commitment *c, uint8_t root_out[32]);

@@ -498,6 +498,74 @@ inline std::unique_ptr<TraceCommitment<E>> build_resident_constraint_commitment_
     return std::make_unique<TraceCommitment<E>>(h, 1, num_cols * E::EXTENSION_DEGREE);
 }
 
+// ConstraintEvaluationTable (constraints/evaluation_table.rs:25-37) left on the device: the columns a constraint program
+// (wf_cprog: Air::evaluate_transition and the boundary constraints as a straight-line program, see wf_lde.h) evaluates over the
+// constraint evaluation domain from the resident LDE of packed trace `trace_index` -- ConstraintEvaluator::evaluate
+// (constraints/evaluator.rs:74-241) for the main segment.  E is the field the program's E constants live in.
+template <class E>
+class ConstraintEvaluations {
+  public:
+    ConstraintEvaluations(const TraceCommitment<typename E::BaseField> &trace, uint32_t trace_index, const wf_cprog &program,
+                          size_t ce_blowup) {
+        wf_check(wf_constraint_evaluate(trace.handle(), trace_index, &program, E::EXTENSION_DEGREE,
+                                        ilog2_exact(ce_blowup, "constraint evaluation blowup"), &h_));
+    }
+    ~ConstraintEvaluations() { wf_evaluations_destroy(h_); }
+    ConstraintEvaluations(const ConstraintEvaluations &) = delete;
+    ConstraintEvaluations &operator=(const ConstraintEvaluations &) = delete;
+    size_t num_columns() const {
+        uint32_t n = 0;
+        wf_check(wf_evaluations_info(h_, &n, nullptr, nullptr));
+        return n;
+    }
+    size_t num_rows() const {  // the constraint evaluation domain's size
+        uint64_t ce = 0;
+        wf_check(wf_evaluations_info(h_, nullptr, &ce, nullptr));
+        return (size_t)ce;
+    }
+    std::vector<E> column(size_t index) const {  // waits for the evaluation
+        std::vector<E> out(num_rows());
+        wf_check(wf_evaluations_read(h_, (uint32_t)index, out.data()));
+        return out;
+    }
+    const wf_evaluations *handle() const { return h_; }
+
+  private:
+    wf_evaluations *h_ = nullptr;
+};
+
+// The constraint side from evaluation tables that are already on the device (one per packed trace, divisors[i][j] going with
+// column j of tables[i]): ConstraintEvaluationTable::into_comb_poly, the final_coeff combination, into_poly and
+// build_constraint_commitment without a column visiting the host.
+template <class E>
+inline std::unique_ptr<TraceCommitment<E>> build_resident_constraint_commitment_from_device_tables(
+    const Prover &prover, const std::vector<const ConstraintEvaluations<E> *> &tables, const std::vector<std::vector<wf_divisor>> &divisors,
+    const E &final_coeff, size_t num_cols, const StarkDomain &domain) {
+    if (tables.empty() || tables.size() != divisors.size()) throw std::invalid_argument("one list of divisors per evaluation table is required");
+    wf_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.field = E::FIELD;
+    p.ext_degree = E::EXTENSION_DEGREE;
+    p.log2_trace_len = ilog2_exact(domain.trace_length(), "trace length");
+    p.log2_blowup = ilog2_exact(domain.trace_to_lde_blowup(), "blowup factor");
+    p.n_cols = (uint32_t)num_cols;
+    p.n_traces = 1;
+    p.digest_bytes = 32;
+    p.hasher = prover.hasher();
+    unsigned __int128 off = domain.offset();
+    std::memcpy(p.domain_offset, &off, 16);
+    std::vector<const wf_evaluations *> handles;
+    std::vector<const wf_divisor *> divs;
+    for (size_t i = 0; i < tables.size(); i++) {
+        if (divisors[i].size() != tables[i]->num_columns()) throw std::invalid_argument("one divisor per column is required");
+        handles.push_back(tables[i]->handle());
+        divs.push_back(divisors[i].data());
+    }
+    wf_commitment *h = nullptr;
+    wf_check(wf_constraint_commit_from_device_tables(prover.context(), &p, handles.data(), divs.data(), handles.size(), &final_coeff, nullptr, &h));
+    return std::make_unique<TraceCommitment<E>>(h, 1, num_cols * E::EXTENSION_DEGREE);
+}
+
 // ------------------------------------------------------------------------------------------------- FRI prover
 struct FriOptions {  // fri/src/options.rs:16-93
     size_t blowup_factor, folding_factor, remainder_max_degree;

@@ -25,6 +25,13 @@
 //! cross the boundary as the Montgomery residues the reference keeps in memory (`math/src/field/f64/mod.rs:48-53`),
 //! f128 as canonical `u128`, extension elements as consecutive base elements (`extensions/quadratic.rs:26-28`).
 //!
+//! The constraint evaluation between the two commitments (`prover/src/lib.rs:386-410`) has a resident form too:
+//! `wf_constraint_evaluate` runs a constraint program (`wf_cprog`, include/wf_lde.h) on the resident trace LDE.  This crate
+//! does not bind it yet and has no tracer: the program is what `Air::evaluate_transition` does to a frame, so running that
+//! method once on an element type that records additions, subtractions and products (with `frame.current()[c]` /
+//! `frame.next()[c]` as the CUR / NEXT sources and the periodic values as TABLE sources) yields it; the boundary constraints
+//! add `(cur[c] - value) * coefficient` columns.
+//!
 //! Needs `RowMatrix::from_raw_parts` (winter-prover-rowmatrix.patch).  This crate has NOT been compiled: the
 //! environment that produced libwf_lde.so has no Rust toolchain.  What is tested there is the C ABI itself
 //! (tests/c/test_abi.c, the ctypes and C++ clients).

@@ -35,6 +35,8 @@ SYMBOLS = [
     "wf_comm_max_f64", "wf_comm_gather_f64", "wf_comm_info", "wf_shard_proofs", "wf_shard_cosets", "wf_shard_route", "wf_comm_all_gather_leaf_shards",
     "wf_trace_commit_sharded_dev", "wf_trace_commit_sharded_resident", "wf_sharded_commitment_destroy",
     "wf_sharded_commitment_root", "wf_sharded_commitment_query", "wf_sharded_commitment_polys",
+    "wf_constraint_evaluate", "wf_evaluations_info", "wf_evaluations_read", "wf_evaluations_destroy",
+    "wf_constraint_commit_from_device_tables",
 ]
 
 
@@ -69,6 +71,53 @@ class Divisor(C.Structure):
 class EvaluationTable(C.Structure):
     """wf_evaluation_table: the columns of one ConstraintEvaluationTable with their divisors."""
     _fields_ = [("columns", C.c_void_p), ("divisors", C.POINTER(Divisor)), ("n_columns", C.c_uint32)]
+
+
+# enum wf_cprog_op / wf_cprog_src (constraint programs)
+CP_ADD, CP_SUB, CP_MUL = 1, 2, 3
+CP_REG, CP_CUR, CP_NEXT, CP_CONST, CP_ECONST, CP_TABLE, CP_X = 0, 1, 2, 3, 4, 5, 6
+
+
+class CprogInstr(C.Structure):
+    """wf_cprog_instr: dst = a op b."""
+    _fields_ = [("op", C.c_uint8), ("a_src", C.c_uint8), ("b_src", C.c_uint8), ("reserved0", C.c_uint8),
+                ("dst", C.c_uint16), ("a", C.c_uint16), ("b", C.c_uint16), ("reserved1", C.c_uint16)]
+
+
+class CprogTable(C.Structure):
+    """wf_cprog_table: value at `step` is values[(step - shift) mod 2^log2_len]."""
+    _fields_ = [("values", C.c_void_p), ("log2_len", C.c_uint32), ("reserved", C.c_uint32), ("shift", C.c_uint64)]
+
+
+class Cprog(C.Structure):
+    """wf_cprog: a straight-line constraint program."""
+    _fields_ = [("instrs", C.POINTER(CprogInstr)), ("n_instrs", C.c_uint32), ("n_regs", C.c_uint32),
+                ("consts", C.c_void_p), ("n_consts", C.c_uint32), ("econsts", C.c_void_p), ("n_econsts", C.c_uint32),
+                ("tables", C.POINTER(CprogTable)), ("n_tables", C.c_uint32),
+                ("out_regs", C.POINTER(C.c_uint16)), ("n_out", C.c_uint32)]
+
+
+def make_cprog(field, ext_degree, instrs, n_regs, out_regs, consts=None, econsts=None, tables=()):
+    """A wf_cprog from Python values: instrs = [(op, dst, (a_src, a), (b_src, b))], consts / econsts = arrays of elements in
+    memory representation (f64: uint64 residues; f128: (n, 2) uint64; econsts with ext_degree coordinates each), tables =
+    [(values, shift)] with power-of-two lengths.  Returns (Cprog, keep): `keep` holds the arrays the structure points into."""
+    w = ELEM_WORDS[field]
+    ci = (CprogInstr * max(1, len(instrs)))()
+    for k, (op, dst, (a_src, a), (b_src, b)) in zip(ci, instrs):
+        k.op, k.dst, k.a_src, k.a, k.b_src, k.b = op, dst, a_src, a, b_src, b
+    cc = np.ascontiguousarray(consts, dtype=np.uint64) if consts is not None and len(consts) else None
+    ce = np.ascontiguousarray(econsts, dtype=np.uint64) if econsts is not None and len(econsts) else None
+    ct = (CprogTable * max(1, len(tables)))()
+    tv = []
+    for t, (values, shift) in zip(ct, tables):
+        v = np.ascontiguousarray(values, dtype=np.uint64)
+        tv.append(v)
+        n = v.size // w
+        t.values, t.log2_len, t.shift = v.ctypes.data, n.bit_length() - 1, shift
+    co = (C.c_uint16 * max(1, len(out_regs)))(*out_regs)
+    prog = Cprog(ci, len(instrs), n_regs, _p(cc), cc.size // w if cc is not None else 0,
+                 _p(ce), ce.size // (w * ext_degree) if ce is not None else 0, ct, len(tables), co, len(out_regs))
+    return prog, (ci, cc, ce, ct, tv, co)
 
 
 class Query(C.Structure):
@@ -237,6 +286,12 @@ def load():
         L.wf_sharded_commitment_root.argtypes = [vp, vp]
         L.wf_sharded_commitment_query.argtypes = [vp, vp, sz, vp, vp, vp, sz, vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(u32)]
         L.wf_sharded_commitment_polys.argtypes = [vp, C.POINTER(vp)]
+        L.wf_constraint_evaluate.argtypes = [vp, u32, C.POINTER(Cprog), u32, u32, C.POINTER(vp)]
+        L.wf_evaluations_info.argtypes = [vp, pu32, pu64, pu32]
+        L.wf_evaluations_read.argtypes = [vp, u32, vp]
+        L.wf_evaluations_destroy.argtypes = [vp]
+        L.wf_evaluations_destroy.restype = None
+        L.wf_constraint_commit_from_device_tables.argtypes = [vp, PP, vp, vp, sz, vp, vp, C.POINTER(vp)]
         _lib = L
     return _lib
 
@@ -501,6 +556,49 @@ class Context:
                                                   C.byref(h)))
         return Commitment(h, params.field, keep_alive=self, digest_bytes=params.digest_bytes), polys
 
+    def constraint_evaluate(self, trace: "Commitment", trace_index: int, prog, ext_degree: int, log2_ce_blowup: int) -> "Evaluations":
+        """wf_constraint_evaluate: run a constraint program (Cprog, or the (Cprog, keep) pair of make_cprog) for every step of
+        the constraint evaluation domain on the resident LDE of matrix `trace_index`; the columns stay on the device."""
+        if isinstance(prog, tuple):
+            prog = prog[0]
+        h = C.c_void_p()
+        _check(load().wf_constraint_evaluate(trace._h, trace_index, C.byref(prog), ext_degree, log2_ce_blowup, C.byref(h)))
+        return Evaluations(h, trace.field, keep_alive=self)
+
+    def constraint_commit_from_device_tables(self, params: Params, tables, final_coeff=None, want_polys=False):
+        """wf_constraint_commit_from_device_tables: tables = [(Evaluations, [(a, b, exemptions) per column])] per packed trace
+        -- constraint_commit_from_tables with the columns already in device memory."""
+        L = load()
+        _check(L.wf_params_check(C.byref(params), 1))
+        w = ELEM_WORDS[params.field]
+        keep = []
+        handles = (C.c_void_p * len(tables))(*[ev._h for ev, _ in tables])
+        div_ptrs = (C.c_void_p * len(tables))()
+        for i, (_, table_divs) in enumerate(tables):
+            divs = (Divisor * len(table_divs))()
+            for d, (a, b, ex) in zip(divs, table_divs):
+                d.numerator_degree = a
+                raw = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1).tobytes().ljust(16, b"\0")
+                d.numerator_constant[:] = list(raw[:16])
+                if ex is not None and len(ex):
+                    e = np.ascontiguousarray(ex, dtype=np.uint64)
+                    keep.append(e)
+                    d.exemptions = e.ctypes.data
+                    d.n_exemptions = e.size // w
+            keep.append(divs)
+            div_ptrs[i] = C.addressof(divs)
+        fc = np.ascontiguousarray(final_coeff, dtype=np.uint64) if final_coeff is not None else None
+        R = 1 << params.log2_trace_len
+        polys = None
+        if want_polys:
+            shape = (R * params.ext_degree, w) if w > 1 else (R * params.ext_degree,)
+            polys = [np.empty(shape, dtype=np.uint64) for _ in range(params.n_cols)]
+        h = C.c_void_p()
+        _check(L.wf_constraint_commit_from_device_tables(self._h, C.byref(params), handles, div_ptrs, len(tables),
+                                                         _p(fc) if fc is not None else None,
+                                                         _ptr_array(polys) if polys else None, C.byref(h)))
+        return Commitment(h, params.field, keep_alive=self, digest_bytes=params.digest_bytes), polys
+
     def deep_compose(self, field, ext, n, trace_commitments, constraint_commitment, z, trace_coeffs, constraint_coeffs=None,
                      want_poly=True, fri: "FriProver" = None, lde_blowup: int = 0):
         """DeepCompositionPoly::add_trace_polys + add_composition_poly (prover/src/composer/mod.rs:62-193) on resident
@@ -737,6 +835,40 @@ class Commitment:
             out.append([bytes(nodes[k + j]) for j in range(int(counts[i]))])
             k += int(counts[i])
         return rows, ([bytes(x) for x in leaves[:n]], out, depth.value)
+
+
+class Evaluations:
+    """wf_evaluations wrapper: the evaluation columns of one constraint program, resident in HBM."""
+
+    def __init__(self, handle, field, keep_alive=None):
+        self._h = handle
+        self.field = field
+        self._keep_alive = keep_alive
+        if isinstance(keep_alive, Context):
+            keep_alive._adopt(self)
+        n, ce, ext = C.c_uint32(), C.c_uint64(), C.c_uint32()
+        _check(load().wf_evaluations_info(self._h, C.byref(n), C.byref(ce), C.byref(ext)))
+        self.n_columns, self.ce_domain_size, self.ext_degree = n.value, ce.value, ext.value
+
+    def close(self):
+        if self._h:
+            if _alive(self._keep_alive):
+                load().wf_evaluations_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def read(self, column: int) -> np.ndarray:
+        """Column `column`: ce_domain_size elements of E (waits for the evaluation)."""
+        w = ELEM_WORDS[self.field]
+        n = self.ce_domain_size * self.ext_degree
+        out = np.empty((n, w) if w > 1 else (n,), dtype=np.uint64)
+        _check(load().wf_evaluations_read(self._h, column, _p(out)))
+        return out
 
 
 def query_many(requests, parse=True):

@@ -1,4 +1,4 @@
-// libwf_lde.so, unit 5 of 7 -- wf_comm: one process per GPU, the path's exchanges behind the C ABI.
+// libwf_lde.so, unit 5 of 8 -- wf_comm: one process per GPU, the path's exchanges behind the C ABI.
 //
 // The reference has no distributed code (/root/reference/README.md:43 lists a distributed prover as planned only); the
 // sharding follows SURVEY.md §8e:

@@ -81,15 +81,19 @@ __global__ void __launch_bounds__(256) k_acc_column(AccColumnArgs<F> a) {
     ext_store<F, WE>(a.acc + i * WE, v);
 }
 
+// Where the columns of the evaluation tables are: host arrays (copied to the device one by one: wf_constraint_commit_from_tables)
+// or device memory of the context (read in place: wf_constraint_commit_from_device_tables)
+enum ColumnSource { COLUMNS_ON_HOST = 0, COLUMNS_ON_DEVICE = 1 };
+
 // the table's columns -> its combined column in ctx->io[2] (device)
 template <class F, int WE>
-static int combine_table_dev(wf_ctx *ctx, hipStream_t st, const wf_params *p, const wf_evaluation_table *tab, uint32_t log_ce,
-                             std::vector<std::vector<typename F::T>> &keep_alive) {
+static int combine_table_dev(wf_ctx *ctx, hipStream_t st, const wf_params *p, const wf_evaluation_table *tab, ColumnSource source,
+                             uint32_t log_ce, std::vector<std::vector<typename F::T>> &keep_alive) {
     typedef typename F::T T;
     const uint64_t ce = (uint64_t)1 << log_ce;
     const size_t bytes = ce * WE * sizeof(T);
     int rc;
-    if ((rc = ensure(ctx, ctx->io[0], bytes))) return rc;
+    if (source == COLUMNS_ON_HOST && (rc = ensure(ctx, ctx->io[0], bytes))) return rc;
     if ((rc = ensure(ctx, ctx->io[2], bytes))) return rc;
     TableSet *tw;
     if ((rc = root_tables<F>(ctx, log_ce, false, &tw))) return rc;
@@ -120,11 +124,11 @@ static int combine_table_dev(wf_ctx *ctx, hipStream_t st, const wf_params *p, co
                                ce - 1, offset_exp, b, as_pow2l<F>(*tw));
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(hipMemcpyAsync(ctx->io[0].p, tab->columns[j], bytes, hipMemcpyHostToDevice, st));
+        if (source == COLUMNS_ON_HOST) HIP_TRY(hipMemcpyAsync(ctx->io[0].p, tab->columns[j], bytes, hipMemcpyHostToDevice, st));
         AccColumnArgs<F> ka;
         memset(&ka, 0, sizeof(ka));
         ka.acc = (T *)ctx->io[2].p;
-        ka.col = (const T *)ctx->io[0].p;
+        ka.col = source == COLUMNS_ON_HOST ? (const T *)ctx->io[0].p : (const T *)tab->columns[j];
         ka.z = (const T *)ctx->io[3].p;
         ka.ce = ce;
         ka.nz_mask = nz - 1;
@@ -143,7 +147,7 @@ static int combine_table_dev(wf_ctx *ctx, hipStream_t st, const wf_params *p, co
 
 template <class F, int WE>
 static int comb_polys_dev(wf_ctx *ctx, hipStream_t st, const wf_params *p, const void *const *evals, const wf_evaluation_table *tables,
-                          size_t n_tables, uint32_t log_ce, const void *final_coeff, void *d_polys,
+                          ColumnSource source, size_t n_tables, uint32_t log_ce, const void *final_coeff, void *d_polys,
                           std::vector<std::vector<typename F::T>> &keep_alive) {
     typedef typename F::T T;
     typedef Ext<F, WE> E;
@@ -165,7 +169,7 @@ static int comb_polys_dev(wf_ctx *ctx, hipStream_t st, const wf_params *p, const
     for (size_t i = 0; i < n_tables; i++) {
         const T *d_combined = (const T *)ctx->io[0].p;
         if (tables) {  // the table's columns divided by their divisors and summed, on the device
-            if ((rc = combine_table_dev<F, WE>(ctx, st, p, &tables[i], log_ce, keep_alive))) return rc;
+            if ((rc = combine_table_dev<F, WE>(ctx, st, p, &tables[i], source, log_ce, keep_alive))) return rc;
             d_combined = (const T *)ctx->io[2].p;
         } else {
             HIP_TRY(hipMemcpyAsync(ctx->io[0].p, evals[i], bytes, hipMemcpyHostToDevice, st));
@@ -193,15 +197,16 @@ static int comb_polys_dev(wf_ctx *ctx, hipStream_t st, const wf_params *p, const
 
 template <class F>
 static int comb_polys_dispatch(wf_ctx *ctx, hipStream_t st, const wf_params *p, const void *const *evals,
-                               const wf_evaluation_table *tables, size_t n_tables, uint32_t log_ce, const void *final_coeff, void *d_polys) {
+                               const wf_evaluation_table *tables, ColumnSource source, size_t n_tables, uint32_t log_ce,
+                               const void *final_coeff, void *d_polys) {
     std::vector<std::vector<typename F::T>> keep_alive;  // host tables read by queued copies
     int rc;
     switch (p->ext_degree) {
-        case 1: rc = comb_polys_dev<F, 1>(ctx, st, p, evals, tables, n_tables, log_ce, final_coeff, d_polys, keep_alive); break;
-        case 2: rc = comb_polys_dev<F, 2>(ctx, st, p, evals, tables, n_tables, log_ce, final_coeff, d_polys, keep_alive); break;
+        case 1: rc = comb_polys_dev<F, 1>(ctx, st, p, evals, tables, source, n_tables, log_ce, final_coeff, d_polys, keep_alive); break;
+        case 2: rc = comb_polys_dev<F, 2>(ctx, st, p, evals, tables, source, n_tables, log_ce, final_coeff, d_polys, keep_alive); break;
         default:
             if constexpr (F::FIELD_ID == 1)
-                rc = comb_polys_dev<F, 3>(ctx, st, p, evals, tables, n_tables, log_ce, final_coeff, d_polys, keep_alive);
+                rc = comb_polys_dev<F, 3>(ctx, st, p, evals, tables, source, n_tables, log_ce, final_coeff, d_polys, keep_alive);
             else
                 rc = fail(WF_ERR_EXTENSION, "f128 has no cubic extension");
     }
@@ -214,8 +219,8 @@ static int comb_polys_dispatch(wf_ctx *ctx, hipStream_t st, const wf_params *p, 
 using namespace wf;
 
 static int constraint_commit_from_impl(wf_ctx *ctx, const wf_params *p, const void *const *combined_evaluations,
-                                       const wf_evaluation_table *tables, size_t n_tables, size_t ce_domain_size, const void *final_coeff,
-                                       void *const *polys_out, wf_commitment **out) {
+                                       const wf_evaluation_table *tables, ColumnSource source, size_t n_tables, size_t ce_domain_size,
+                                       const void *final_coeff, void *const *polys_out, wf_commitment **out) {
     if (!ctx) return fail(WF_ERR_ARG, "ctx is null");
     if (!out) return fail(WF_ERR_ARG, "out is null");
     int rc = check_params(p, true);
@@ -274,8 +279,8 @@ static int constraint_commit_from_impl(wf_ctx *ctx, const wf_params *p, const vo
     if ((rc = commitment_alloc(ctx, p, true, &c, &dense))) return rc;
     hipStream_t st = ctx->stream;
     rc = p->field == WF_FIELD_F64
-             ? comb_polys_dispatch<F64>(ctx, st, p, combined_evaluations, tables, n_tables, log_ce, final_coeff, c->polys)
-             : comb_polys_dispatch<F128>(ctx, st, p, combined_evaluations, tables, n_tables, log_ce, final_coeff, c->polys);
+             ? comb_polys_dispatch<F64>(ctx, st, p, combined_evaluations, tables, source, n_tables, log_ce, final_coeff, c->polys)
+             : comb_polys_dispatch<F128>(ctx, st, p, combined_evaluations, tables, source, n_tables, log_ce, final_coeff, c->polys);
     if (rc == 0)
         rc = p->field == WF_FIELD_F64 ? constraint_commit_dev<F64>(ctx, p, c->polys, c->lde, c->leaves, c->nodes, st, dense)
                                       : constraint_commit_dev<F128>(ctx, p, c->polys, c->lde, c->leaves, c->nodes, st, dense);
@@ -299,13 +304,39 @@ extern "C" {
 int wf_constraint_commit_from_evaluations(wf_ctx *ctx, const wf_params *p, const void *const *combined_evaluations, size_t n_tables,
                                           size_t ce_domain_size, const void *final_coeff, void *const *polys_out, wf_commitment **out) {
     if (!combined_evaluations) return fail(WF_ERR_ARG, "no evaluation tables");
-    return constraint_commit_from_impl(ctx, p, combined_evaluations, nullptr, n_tables, ce_domain_size, final_coeff, polys_out, out);
+    return constraint_commit_from_impl(ctx, p, combined_evaluations, nullptr, COLUMNS_ON_HOST, n_tables, ce_domain_size, final_coeff, polys_out, out);
 }
 
 int wf_constraint_commit_from_tables(wf_ctx *ctx, const wf_params *p, const wf_evaluation_table *tables, size_t n_tables,
                                      size_t ce_domain_size, const void *final_coeff, void *const *polys_out, wf_commitment **out) {
     if (!tables) return fail(WF_ERR_ARG, "no evaluation tables");
-    return constraint_commit_from_impl(ctx, p, nullptr, tables, n_tables, ce_domain_size, final_coeff, polys_out, out);
+    return constraint_commit_from_impl(ctx, p, nullptr, tables, COLUMNS_ON_HOST, n_tables, ce_domain_size, final_coeff, polys_out, out);
+}
+
+// The same with the tables' columns already in device memory (wf_constraint_evaluate): the chain above reads them in place.
+int wf_constraint_commit_from_device_tables(wf_ctx *ctx, const wf_params *p, const wf_evaluations *const *tables,
+                                            const wf_divisor *const *divisors, size_t n_tables, const void *final_coeff,
+                                            void *const *polys_out, wf_commitment **out) {
+    if (!ctx) return fail(WF_ERR_ARG, "ctx is null");
+    if (!p) return fail(WF_ERR_ARG, "params is null");
+    if (!tables || !divisors || n_tables == 0) return fail(WF_ERR_ARG, "no evaluation tables");
+    std::vector<wf_evaluation_table> tabs(n_tables);
+    std::vector<std::vector<const void *>> cols(n_tables);
+    for (size_t i = 0; i < n_tables; i++) {
+        const wf_evaluations *e = tables[i];
+        if (!e || !divisors[i]) return fail(WF_ERR_ARG, "evaluation table %zu is null", i);
+        if (e->ctx != ctx || e->ctx_generation != ctx->generation) return fail(WF_ERR_ARG, "evaluation table %zu belongs to another context", i);
+        if (e->ce != tables[0]->ce) return fail(WF_ERR_ARG, "evaluation table %zu has %llu steps, table 0 has %llu", i, (unsigned long long)e->ce, (unsigned long long)tables[0]->ce);
+        if (e->field != p->field || e->ext != p->ext_degree)
+            return fail(WF_ERR_ARG, "evaluation table %zu holds elements of field %u, extension degree %u (params: %u, %u)", i, e->field, e->ext, p->field, p->ext_degree);
+        const size_t colb = (size_t)e->ce * e->ext * wf_elem_bytes(e->field);
+        cols[i].resize(e->n_columns);
+        for (uint32_t j = 0; j < e->n_columns; j++) cols[i][j] = (const char *)e->cols + (size_t)j * colb;
+        tabs[i].columns = cols[i].data();
+        tabs[i].divisors = divisors[i];
+        tabs[i].n_columns = e->n_columns;
+    }
+    return constraint_commit_from_impl(ctx, p, nullptr, tabs.data(), COLUMNS_ON_DEVICE, n_tables, (size_t)tables[0]->ce, final_coeff, polys_out, out);
 }
 
 }  // extern "C"

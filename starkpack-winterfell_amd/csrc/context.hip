@@ -1,4 +1,4 @@
-// libwf_lde.so, unit 1 of 7 -- the context: errors, the registry of live contexts, the buffer pool, profiling marks,
+// libwf_lde.so, unit 1 of 8 -- the context: errors, the registry of live contexts, the buffer pool, profiling marks,
 // column upload / download, parameter validation and the size helpers of the C ABI (include/wf_lde.h).
 // There is deliberately no CPU fallback: every compute entry point needs a HIP device.
 #include "wf_internal.hpp"

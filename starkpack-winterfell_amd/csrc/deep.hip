@@ -1,4 +1,4 @@
-// libwf_lde.so, unit 6 of 7 -- the DEEP composition polynomial on resident commitments (deep.hpp holds kernels and host code).
+// libwf_lde.so, unit 6 of 8 -- the DEEP composition polynomial on resident commitments (deep.hpp holds kernels and host code).
 #include "wf_internal.hpp"
 
 #include "kernels.hpp"

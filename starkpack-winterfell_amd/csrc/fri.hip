@@ -1,4 +1,4 @@
-// libwf_lde.so, unit 4 of 7 -- FRI: layer commitments, the degree-respecting projection, and the resident
+// libwf_lde.so, unit 4 of 8 -- FRI: layer commitments, the degree-respecting projection, and the resident
 // FRI prover (FriProver::build_layers / build_layer / set_remainder, /root/reference/fri/src/prover/mod.rs:172-227).
 #include "wf_internal.hpp"
 

@@ -12,70 +12,6 @@
 
 namespace wf {
 
-// Extension-field product.  f64: x^2 = x - 2 (f64/mod.rs:401-417), x^3 = x + 1 (:446-472); f128: x^2 = x + 1
-// (f128/mod.rs:273-279).  Any correct formula gives the reference's values (unique reduced representatives).
-template <class F, int W>
-struct Ext {
-    typedef typename F::T T;
-    T c[W];
-};
-
-template <class F, int WE>
-__device__ __forceinline__ Ext<F, WE> ext_zero() {
-    Ext<F, WE> r;
-#pragma unroll
-    for (int w = 0; w < WE; w++) r.c[w] = F::zero();
-    return r;
-}
-template <class F, int WE>
-__device__ __forceinline__ Ext<F, WE> ext_add(Ext<F, WE> a, const Ext<F, WE> &b) {
-#pragma unroll
-    for (int w = 0; w < WE; w++) a.c[w] = F::add(a.c[w], b.c[w]);
-    return a;
-}
-template <class F, int WE>
-__device__ __forceinline__ Ext<F, WE> ext_load(const typename F::T *p) {
-    Ext<F, WE> r;
-#pragma unroll
-    for (int w = 0; w < WE; w++) r.c[w] = p[w];
-    return r;
-}
-template <class F, int WE>
-__device__ __forceinline__ void ext_store(typename F::T *p, const Ext<F, WE> &v) {
-#pragma unroll
-    for (int w = 0; w < WE; w++) p[w] = v.c[w];
-}
-
-template <class F, int W>
-__host__ __device__ __forceinline__ Ext<F, W> ext_mul(const Ext<F, W> &a, const Ext<F, W> &b) {
-    typedef typename F::T T;
-    Ext<F, W> r;
-    if constexpr (W == 1) {
-        r.c[0] = F::mul(a.c[0], b.c[0]);
-    } else if constexpr (W == 2) {
-        const T a0b0 = F::mul(a.c[0], b.c[0]), a1b1 = F::mul(a.c[1], b.c[1]);
-        const T cross = F::sub(F::sub(F::mul(F::add(a.c[0], a.c[1]), F::add(b.c[0], b.c[1])), a0b0), a1b1);  // a0b1+a1b0
-        if constexpr (F::FIELD_ID == 1) {  // phi^2 = phi - 2
-            r.c[0] = F::sub(a0b0, F::add(a1b1, a1b1));
-            r.c[1] = F::add(cross, a1b1);
-        } else {  // phi^2 = phi + 1
-            r.c[0] = F::add(a0b0, a1b1);
-            r.c[1] = F::add(cross, a1b1);
-        }
-    } else {  // cubic over f64: phi^3 = phi + 1, phi^4 = phi^2 + phi
-        T d[5];
-        d[0] = F::mul(a.c[0], b.c[0]);
-        d[1] = F::add(F::mul(a.c[0], b.c[1]), F::mul(a.c[1], b.c[0]));
-        d[2] = F::add(F::add(F::mul(a.c[0], b.c[2]), F::mul(a.c[1], b.c[1])), F::mul(a.c[2], b.c[0]));
-        d[3] = F::add(F::mul(a.c[1], b.c[2]), F::mul(a.c[2], b.c[1]));
-        d[4] = F::mul(a.c[2], b.c[2]);
-        r.c[0] = F::add(d[0], d[3]);
-        r.c[1] = F::add(F::add(d[1], d[3]), d[4]);
-        r.c[2] = F::add(d[2], d[4]);
-    }
-    return r;
-}
-
 // transpose_slice: out[i][j] = src[i + j * rows]; one thread per element, j fastest: the N threads of a row write its
 // N * W elements back to back (stores fully coalesced) and each of the N source streams is read in runs of 64 / N
 // elements per wave (with i fastest every 16-byte store went to a different row: 1.4 TB/s)

@@ -1,4 +1,4 @@
-// libwf_lde.so, unit 7 of 7 -- the proof-of-work of the query seed: wf_grind_seeds (ProverChannel::grind_query_seed,
+// libwf_lde.so, unit 7 of 8 -- the proof-of-work of the query seed: wf_grind_seeds (ProverChannel::grind_query_seed,
 // prover/src/channel.rs:182-198) on the kernels of grind_kernels.hpp and the window schedule of grind_plan.hpp.
 #include "wf_internal.hpp"
 

@@ -1,4 +1,4 @@
-// libwf_lde.so, unit 2 of 7 -- the commitment path: pass planner, every launch of the transform / hashing / tree kernels,
+// libwf_lde.so, unit 2 of 8 -- the commitment path: pass planner, every launch of the transform / hashing / tree kernels,
 // and the C ABI of the path and of the math::fft building blocks.  Replaces Prover::build_trace_commitment /
 // build_constraint_commitment (/root/reference/prover/src/lib.rs:615-715) and the math::fft / crypto functions they call.
 #include "wf_internal.hpp"

@@ -1,4 +1,4 @@
-// libwf_lde.so, unit 3 of 7 -- resident commitments: the LDE, the tree and the polynomials stay in HBM (what TraceCommitment
+// libwf_lde.so, unit 3 of 8 -- resident commitments: the LDE, the tree and the polynomials stay in HBM (what TraceCommitment
 // / ConstraintCommitment own in the reference: prover/src/trace/commitment.rs:21-26, constraints/commitment.rs:21-24);
 // synchronous and asynchronous construction from host columns, the query service (rows + BatchMerkleProof), the
 // out-of-domain evaluation, and the resident form of the coset-sharded commitment with its collective queries.

@@ -4,7 +4,7 @@
 
 #include "wf_internal.hpp"
 
-#include "kernels.hpp"
+#include "pow2l.hpp"
 
 using namespace wf;
 

@@ -7,6 +7,7 @@
 //   comm.hip      wf_comm: RCCL / caller transport, partition rules
 //   deep.hip      DEEP composition polynomial
 //   grind.hip     the nonce search of the query seed (wf_grind_seeds)
+//   constraint_eval.hip  constraint programs on a resident trace LDE (wf_constraint_evaluate, wf_evaluations)
 // A function that launches kernels lives in exactly one unit (kernels are templates / static functions of the headers, so
 // each is compiled once, where it is launched); the other units reach it through the non-template entry points below.
 #pragma once
@@ -297,6 +298,27 @@ struct wf_commitment {
 void free_commitment(wf_commitment *c);
 int commitment_alloc(wf_ctx *ctx, const wf_params *p, bool constraint, wf_commitment **out, bool *dense_out);
 wf_commitment *commitment_new(wf_ctx *ctx);  // zeroed handle bound to ctx (FRI layers fill it themselves)
+
+// ------------------------------------------------------------------------------------------------- constraint_eval.hip
+// The evaluation columns of one constraint program over the constraint evaluation domain, resident (what
+// ConstraintEvaluationTable owns in the reference: prover/src/constraints/evaluation_table.rs:25-37).  path.hip reads the
+// columns in place (wf_constraint_commit_from_device_tables).
+struct wf_evaluations {
+    wf_ctx *ctx = nullptr;
+    uint64_t ctx_generation = 0;
+    int device = 0;
+    uint32_t field = 0, ext = 0, n_columns = 0;
+    uint64_t ce = 0;
+    void *cols = nullptr;  // [n_columns][ce] elements of E
+    size_t cols_bytes = 0;
+    void *prog = nullptr;  // the planned program as the kernel reads it (instructions, constants, tables)
+    size_t prog_bytes = 0;
+    // Its host image, PINNED (hipHostMalloc): the upload is queued on the stream and the call returns without waiting (a copy
+    // from pageable memory would either block the host until everything queued in front of it has drained, or read the image
+    // after the call); `uploaded` is recorded behind the copy and wf_evaluations_destroy waits for it before the image goes.
+    void *prog_host = nullptr;
+    hipEvent_t uploaded = nullptr;
+};
 
 // ------------------------------------------------------------------------------------------------- fri.hip
 // (the DEEP composition hands its polynomial straight to a prover: deep.hip reads its field / extension / offset)
