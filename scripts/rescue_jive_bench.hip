@@ -14,7 +14,6 @@
 #include <vector>
 
 #include "keccak_kernels.hpp"
-#include "rescue_jive_kernels.hpp"
 #include "rescue_kernels.hpp"
 
 using namespace wf;
@@ -84,8 +83,9 @@ static void level_form1(const void *children, void *nodes, uint64_t n_par) {
 
 static void subtree(const void *children, void *nodes, uint64_t n_children, uint32_t levels) {
     const uint64_t n_par = n_children >> 1;
-    hipLaunchKernelGGL(k_rpjive_merkle_subtree, dim3((uint32_t)((n_par + RPJIVE_SUBTREE_SPAN - 1) / RPJIVE_SUBTREE_SPAN)),
-                       dim3(RPJIVE_SUBTREE_THREADS), 0, 0, (const uint64_t *)children, (uint64_t *)nodes, n_children, levels);
+    constexpr MerklePlan P = MERKLE_PLAN_RPJIVE;
+    hipLaunchKernelGGL(k_merkle_subtree_lanes<rpj::Lanes>, dim3((uint32_t)((n_par + P.subtree_span - 1) / P.subtree_span)),
+                       dim3(P.subtree_threads), 0, 0, (const uint64_t *)children, (uint64_t *)nodes, n_children, levels);
 }
 
 static void tree(const void *leaves, uint64_t n_leaves, void *nodes, uint32_t level_min_log) {  // the plan of run_merkle with the switch at 2^level_min_log
@@ -138,7 +138,7 @@ int main(int argc, char **argv) {
         CHECK(hipMemcpy(leaves, h.data(), n * 32, hipMemcpyHostToDevice));
     }
     if (!quick) {
-        printf("one tree level, milliseconds (form 1 = k_merkle_level<rpj::Merge>, form 2 = k_rpjive_merkle_subtree with one level)\n");
+        printf("one tree level, milliseconds (form 1 = k_merkle_level<rpj::Merge>, form 2 = k_merkle_subtree_lanes<rpj::Lanes> with one level)\n");
         for (uint32_t lg = 10; lg <= 22; lg++) {
             const uint64_t n_par = 1ull << lg;
             const float m1 = timeit([&] { level_form1(leaves, nodes, n_par); }, 5);

@@ -42,9 +42,9 @@ LOGICAL = [
     ("hash_rows", ["k_hash_rows", "k_hash_chunks", "k_hash_merge_chunks"]),
     # k_merkle_level also matches k_merkle_level2.  The tree kernels are templates on the hasher's merge policy
     # (k_merkle_level<wf::b3::Merge<8>>, <wf::k3::Merge>, <wf::rp::Merge>): the substrings take every hasher's, and
-    # k_rp64_merkle_subtree (the lane-form top of the Rp64_256 tree) is listed so that the Sha3_256 and Rp64_256 trees fall
-    # into this group whole, deliberately.  cfg 2 (BLAKE3) launches k_merkle_level2 x3 and k_merkle_subtree x2 as before.
-    # (k_rpjive_merkle_subtree: the same for the RpJive64_256 tree)
+    # k_merkle_subtree also matches k_merkle_subtree_lanes<L> (the lane-form top of the Rp64_256 and RpJive64_256 trees), so
+    # that every hasher's tree falls into this group whole, deliberately; the two names that kernel had before it became one
+    # template stay listed for older traces.  cfg 2 (BLAKE3) launches k_merkle_level2 x3 and k_merkle_subtree x2 as before.
     ("merkle", ["k_merkle_level", "k_merkle_subtree", "k_rp64_merkle_subtree", "k_rpjive_merkle_subtree"])
 ]
 # Round 4 calibration: the SECOND strided evaluation pass of cfg 3 must read the 17.18 GB intermediate exactly once (nothing can

@@ -6,6 +6,7 @@
 #include <atomic>
 
 #include "field.hpp"
+#include "hasher_table.hpp"
 
 using namespace wf;
 
@@ -314,27 +315,28 @@ int check_params(const wf_params *p, bool constraint) {
 }
 
 static const char *hasher_name(uint32_t hasher) {
-    return hasher == WF_HASH_BLAKE3          ? "BLAKE3"
-           : hasher == WF_HASH_SHA3_256      ? "Sha3_256"
-           : hasher == WF_HASH_RP64_256      ? "Rp64_256"
-           : hasher == WF_HASH_RPJIVE64_256 ? "RpJive64_256"
-           : hasher == WF_HASH_GRIFFINJIVE64_256 ? "GriffinJive64_256"
-                                             : nullptr;
+    const HasherRow *r = hasher_row(hasher);
+    return r ? r->name : nullptr;
 }
 
 // a known hasher id, and a digest size that hasher has (BLAKE3: 32 or 24, the others 32)
 int check_hasher_pair(uint32_t hasher, uint32_t digest_bytes) {
-    if (!hasher_name(hasher))
-        return fail(WF_ERR_DIGEST, "unknown hasher id %u (0 = BLAKE3, 1 = Sha3_256, 16 = Rp64_256, 18 = RpJive64_256, 20 = GriffinJive64_256)", hasher);
-    if (hasher != WF_HASH_BLAKE3 && digest_bytes != 32)
-        return fail(WF_ERR_DIGEST, "%s has 32-byte digests, got digest_bytes %u", hasher_name(hasher), digest_bytes);
+    const HasherRow *r = hasher_row(hasher);
+    if (!r) {
+        std::string known;
+        for (const HasherRow &k : HASHERS) known += (known.empty() ? "" : ", ") + std::to_string(k.id) + " = " + k.name;
+        return fail(WF_ERR_DIGEST, "unknown hasher id %u (%s)", hasher, known.c_str());
+    }
+    if (!r->digest24 && digest_bytes != 32)
+        return fail(WF_ERR_DIGEST, "%s has 32-byte digests, got digest_bytes %u", r->name, digest_bytes);
     return 0;
 }
 
 // an element-digest hasher hashes elements of its own field only
 int check_hasher_field(uint32_t hasher, uint32_t field) {
-    if ((hasher == WF_HASH_RP64_256 || hasher == WF_HASH_RPJIVE64_256 || hasher == WF_HASH_GRIFFINJIVE64_256) && field != WF_FIELD_F64)
-        return fail(WF_ERR_FIELD, "%s hashes elements of the f64 field only (field id %u)", hasher_name(hasher), field);
+    const HasherRow *r = hasher_row(hasher);
+    if (r && r->f64_only && field != WF_FIELD_F64)
+        return fail(WF_ERR_FIELD, "%s hashes elements of the f64 field only (field id %u)", r->name, field);
     return 0;
 }
 
@@ -479,7 +481,7 @@ int wf_ctx_set_digest_bytes(wf_ctx *ctx, uint32_t digest_bytes) {
     if (!ctx) return fail(WF_ERR_ARG, "ctx is null");
     if (digest_bytes != 32 && digest_bytes != 24)
         return fail(WF_ERR_DIGEST, "digest_bytes must be 32 (Blake3_256) or 24 (Blake3_192), got %u", digest_bytes);
-    if (digest_bytes != 32 && ctx->hasher != WF_HASH_BLAKE3)
+    if (digest_bytes != 32 && !hasher_row(ctx->hasher)->digest24)
         return fail(WF_ERR_DIGEST, "the context hashes with %s, which has 32-byte digests (got digest_bytes %u)",
                     hasher_name(ctx->hasher), digest_bytes);
     WF_ENTER(ctx, nullptr);

@@ -136,84 +136,18 @@ WF_HD void permute(uint64_t (&s)[STATE]) {
 }
 
 // ------------------------------------------------------------------------------------ sponge and compression
-// hash_elements of n base elements; next() returns them in order as Montgomery residues (the stored form).  One permutation
-// call site; state elements are addressed with compile-time indices only.  Only the last block can be partial (take < RATE
-// exactly when fewer than RATE elements remain), which is where the padding is set.  out = the canonical digest words.
+// jive_dev.hpp on this permutation: the rate (and the digest) in places 0..3, the "partial block" flag in place 4.
+struct Perm {
+    static constexpr int RATE_AT = 0, FLAG_AT = 4;
+    static WF_HD void permute(uint64_t (&s)[STATE]) { gfj::permute(s); }
+};
 template <class Next>
-WF_HD void hash_elements(uint64_t n, Next &&next, uint64_t (&out)[DIGEST]) {
-    uint64_t s[STATE];
-#pragma unroll
-    for (int i = 0; i < STATE; i++) s[i] = 0;
-    s[RATE] = (n % RATE) != 0 ? F64::one() : 0;
-    uint64_t rem = n;
-    while (rem) {
-        const uint32_t take = rem < (uint64_t)RATE ? (uint32_t)rem : (uint32_t)RATE;
-#pragma unroll
-        for (int i = 0; i < RATE; i++) {
-            if ((uint32_t)i < take) s[i] = F64::add(s[i], next());
-            else s[i] = (uint32_t)i == take ? F64::one() : 0;
-        }
-        permute(s);
-        rem -= take;
-    }
-#pragma unroll
-    for (int i = 0; i < DIGEST; i++) out[i] = F64::to_canonical(s[i]);
-}
-
-// The Jive compression of a state already in Montgomery form: out[i] = init[i] + init[4+i] + fin[i] + fin[4+i], canonical.
-// (The sums of the initial state are formed before the permutation: 4 values live across it, not 8.)
-WF_HD void compress(uint64_t (&s)[STATE], uint64_t (&out)[DIGEST]) {
-    uint64_t pre[DIGEST];
-#pragma unroll
-    for (int i = 0; i < DIGEST; i++) pre[i] = F64::add(s[i], s[DIGEST + i]);
-    permute(s);
-#pragma unroll
-    for (int i = 0; i < DIGEST; i++) out[i] = F64::to_canonical(F64::add(pre[i], F64::add(s[i], s[DIGEST + i])));
-}
-
-// merge: the digest words of the two children (4 + 4, as stored: canonical, or any u64 from a caller) -> canonical digest.
-WF_HD void merge(const uint64_t (&in)[8], uint64_t (&out)[DIGEST]) {
-    uint64_t s[STATE];
-#pragma unroll
-    for (int i = 0; i < STATE; i++) s[i] = rp::elem_new(in[i]);
-    compress(s, out);
-}
-
-// merge_with_int (griffin64_256_jive/mod.rs:183-206) on a seed already in Montgomery form (the search kernel converts its
-// seed once): the seed in places 0..3, BaseElement::new(value) in place 4 and 5 in place 7 when value < p; otherwise value / p
-// in place 5 as well and 6 in place 7.  p <= value < 2^64 < 2 p, so that quotient is 1.
-WF_HD void merge_with_int_mont(const uint64_t (&seed)[DIGEST], uint64_t value, uint64_t (&out)[DIGEST]) {
-    const bool wide = value >= F64::P;
-    uint64_t s[STATE];
-#pragma unroll
-    for (int i = 0; i < DIGEST; i++) s[i] = seed[i];
-    s[4] = rp::elem_new(value);
-    s[5] = wide ? F64::one() : 0;
-    s[6] = 0;
-    s[7] = rp::elem_new(wide ? 6 : 5);
-    compress(s, out);
-}
-
-// The same on the seed's digest words as stored (canonical, or any u64 from a caller: read as BaseElement::new reads them).
-WF_HD void merge_with_int(const uint64_t (&seed)[DIGEST], uint64_t value, uint64_t (&out)[DIGEST]) {
-    uint64_t m[DIGEST];
-#pragma unroll
-    for (int i = 0; i < DIGEST; i++) m[i] = rp::elem_new(seed[i]);
-    merge_with_int_mont(m, value, out);
-}
-
-// The hasher as the tree kernels (Merge) and the lane-per-row leaf kernel (Absorb) take it, as rpj::Merge / rpj::Absorb.
-struct Merge {
-    using W = uint64_t;
-    static constexpr int NW = DIGEST;
-    static constexpr bool HAS_QUAD = false;
-    static WF_HD void merge(const W (&in)[2 * NW], W (&out)[NW]) { gfj::merge(in, out); }
-};
-struct Absorb {
-    static constexpr bool CANONICAL = false;
-    template <class Next>
-    static WF_HD void absorb(uint64_t n, Next &&next, uint64_t (&out)[DIGEST]) { hash_elements(n, next, out); }
-};
+WF_HD void hash_elements(uint64_t n, Next &&next, uint64_t (&out)[DIGEST]) { jive::hash_elements<Perm>(n, next, out); }
+WF_HD void merge(const uint64_t (&in)[8], uint64_t (&out)[DIGEST]) { jive::merge<Perm>(in, out); }
+WF_HD void merge_with_int_mont(const uint64_t (&seed)[DIGEST], uint64_t value, uint64_t (&out)[DIGEST]) { jive::merge_with_int_mont<Perm>(seed, value, out); }
+WF_HD void merge_with_int(const uint64_t (&seed)[DIGEST], uint64_t value, uint64_t (&out)[DIGEST]) { jive::merge_with_int<Perm>(seed, value, out); }
+struct Merge : jive::Merge<Perm> {};
+struct Absorb : jive::Absorb<Perm> {};
 
 }  // namespace gfj
 }  // namespace wf

@@ -91,27 +91,15 @@ extern "C" int wf_grind_seeds(wf_ctx *ctx, const uint8_t *seeds, size_t n_seeds,
     }
     memset(pin + L.best, 0xFF, n_seeds * 8);
     HIP_TRY(hipMemcpyAsync(dev, pin, L.nonces, hipMemcpyHostToDevice, st));
-    GrindPlan plan = ctx->hasher == WF_HASH_RP64_256        ? GRIND_PLAN_RP64
-                     : ctx->hasher == WF_HASH_RPJIVE64_256 ? GRIND_PLAN_RPJIVE
-                     : ctx->hasher == WF_HASH_GRIFFINJIVE64_256 ? GRIND_PLAN_GRIFFIN
-                     : ctx->hasher == WF_HASH_SHA3_256     ? GRIND_PLAN_SHA3
-                                                           : GRIND_PLAN_BLAKE3;
+    GrindPlan plan = hasher_row(ctx->hasher)->grind;
     if (ctx->tune.grind_window_cap_log2) plan.cap_log2 = ctx->tune.grind_window_cap_log2;
     if (ctx->tune.grind_window_log2) plan.first_log2 = ctx->tune.grind_window_log2;
     plan.first_log2 = std::min(plan.first_log2, plan.cap_log2);
     const uint32_t n = (uint32_t)n_seeds;
-    if (ctx->hasher == WF_HASH_RP64_256)
-        rc = grind_run<GrindRp64>(ctx, st, dev, pin, L, n, grinding_factor, nonce_begin, max_nonces, plan);
-    else if (ctx->hasher == WF_HASH_RPJIVE64_256)
-        rc = grind_run<GrindRpJive>(ctx, st, dev, pin, L, n, grinding_factor, nonce_begin, max_nonces, plan);
-    else if (ctx->hasher == WF_HASH_GRIFFINJIVE64_256)
-        rc = grind_run<GrindGriffin>(ctx, st, dev, pin, L, n, grinding_factor, nonce_begin, max_nonces, plan);
-    else if (ctx->hasher == WF_HASH_SHA3_256)
-        rc = grind_run<GrindSha3>(ctx, st, dev, pin, L, n, grinding_factor, nonce_begin, max_nonces, plan);
-    else if (ctx->digest_bytes == 24)
-        rc = grind_run<GrindBlake3<6>>(ctx, st, dev, pin, L, n, grinding_factor, nonce_begin, max_nonces, plan);
-    else
-        rc = grind_run<GrindBlake3<8>>(ctx, st, dev, pin, L, n, grinding_factor, nonce_begin, max_nonces, plan);
+    rc = dispatch_hasher(ctx->hasher, ctx->digest_bytes, [&](auto tag) {
+        typedef typename GrindOf<typename decltype(tag)::Merge>::type G;
+        return grind_run<G>(ctx, st, dev, pin, L, n, grinding_factor, nonce_begin, max_nonces, plan);
+    });
     if (rc) return rc;
     memcpy(nonces_out, pin + L.nonces, n_seeds * 8);
     memcpy(new_seeds_out, pin + L.new_seeds, n_seeds * 32);

@@ -10,12 +10,8 @@
 // No memory traffic beyond the seed (wave-uniform: scalar loads), one relaxed load of best[] per iteration and one atomic
 // per wave that found something.
 #pragma once
-#include "blake3_dev.hpp"
 #include "grind_plan.hpp"
-#include "keccak_dev.hpp"
-#include "rescue_dev.hpp"
-#include "rescue_jive_dev.hpp"
-#include "griffin_dev.hpp"
+#include "hasher_dispatch.hpp"
 
 namespace wf {
 
@@ -64,10 +60,13 @@ struct GrindSha3 {
     }
 };
 
-// Rp64_256, the one-lane-per-permutation form (rp::permute), as the row and wide-level kernels.  The seed's words are read
-// as BaseElement::new reads them (reduced mod p) and kept as Montgomery residues; the test reads the CANONICAL value of digest
-// element 0 (ElementDigest::as_bytes).
-struct GrindRp64 {
+// The element-digest hashers (Rp64_256, RpJive64_256, GriffinJive64_256), each in its one-lane-per-permutation form, as the
+// row and wide-level kernels; M = the hasher's Merge.  The seed's words are read as BaseElement::new reads them (reduced mod p)
+// and kept as Montgomery residues; M::merge_with_int_mont is the hasher's merge_with_int on such a seed (Rp64_256: the sponge
+// of seed || nonce; the Jive hashers: the compression of seed || nonce); the test reads the CANONICAL value of digest element
+// 0 (ElementDigest::as_bytes).
+template <class M>
+struct GrindElem {
     struct Seed {
         uint64_t w[4];
     };
@@ -86,45 +85,25 @@ struct GrindRp64 {
     }
     static __device__ __forceinline__ uint32_t head32(const Seed &s, uint64_t nonce) {
         uint64_t d[4];
-        rp::merge_with_int_mont(s.w, nonce, d);
+        M::merge_with_int_mont(s.w, nonce, d);
         return (uint32_t)d[0];
     }
     static __device__ __forceinline__ void digest(const Seed &s, uint64_t nonce, uint64_t (&out)[4]) {
-        rp::merge_with_int_mont(s.w, nonce, out);
+        M::merge_with_int_mont(s.w, nonce, out);
     }
 };
+// (named structs: k_grind / k_grind_finish are instantiated on, and their traces keyed by, these names)
+struct GrindRp64 : GrindElem<rp::Merge> {};
+struct GrindRpJive : GrindElem<rpj::Merge> {};
+struct GrindGriffin : GrindElem<gfj::Merge> {};
 
-// RpJive64_256, the one-lane-per-permutation form (rpj::permute): the seed read, converted once and kept in scalar registers
-// exactly as GrindRp64 does; merge_with_int is the Jive compression of seed || nonce (rpj::merge_with_int_mont).
-struct GrindRpJive {
-    typedef GrindRp64::Seed Seed;
-    static __device__ __forceinline__ void prepare(const uint64_t *slot, Seed &s) { GrindRp64::prepare(slot, s); }
-    static __device__ __forceinline__ void wave_uniform(Seed &s) { GrindRp64::wave_uniform(s); }
-    static __device__ __forceinline__ uint32_t head32(const Seed &s, uint64_t nonce) {
-        uint64_t d[4];
-        rpj::merge_with_int_mont(s.w, nonce, d);
-        return (uint32_t)d[0];
-    }
-    static __device__ __forceinline__ void digest(const Seed &s, uint64_t nonce, uint64_t (&out)[4]) {
-        rpj::merge_with_int_mont(s.w, nonce, out);
-    }
-};
-
-// GriffinJive64_256 (gfj::permute, one lane per permutation): the seed handling of GrindRp64; merge_with_int is the Jive
-// compression of seed || nonce (gfj::merge_with_int_mont).
-struct GrindGriffin {
-    typedef GrindRp64::Seed Seed;
-    static __device__ __forceinline__ void prepare(const uint64_t *slot, Seed &s) { GrindRp64::prepare(slot, s); }
-    static __device__ __forceinline__ void wave_uniform(Seed &s) { GrindRp64::wave_uniform(s); }
-    static __device__ __forceinline__ uint32_t head32(const Seed &s, uint64_t nonce) {
-        uint64_t d[4];
-        gfj::merge_with_int_mont(s.w, nonce, d);
-        return (uint32_t)d[0];
-    }
-    static __device__ __forceinline__ void digest(const Seed &s, uint64_t nonce, uint64_t (&out)[4]) {
-        gfj::merge_with_int_mont(s.w, nonce, out);
-    }
-};
+// The search policy of a hasher, by its Merge (the tag of dispatch_hasher carries that).
+template <class M> struct GrindOf;
+template <int DW> struct GrindOf<b3::Merge<DW>> { typedef GrindBlake3<DW> type; };
+template <> struct GrindOf<k3::Merge> { typedef GrindSha3 type; };
+template <> struct GrindOf<rp::Merge> { typedef GrindRp64 type; };
+template <> struct GrindOf<rpj::Merge> { typedef GrindRpJive type; };
+template <> struct GrindOf<gfj::Merge> { typedef GrindGriffin type; };
 
 constexpr uint32_t GRIND_THREADS = 256;
 constexpr uint64_t GRIND_NONE = ~(uint64_t)0;  // best[seed] before anything is found

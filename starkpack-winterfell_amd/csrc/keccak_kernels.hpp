@@ -2,7 +2,7 @@
 // rescue_dev.hpp).  The same arguments, device layouts and roles as the BLAKE3 kernels of kernels.hpp (32-byte digest slots).
 // A sponge absorbs sequentially: there is no chunk tree, so one kernel hashes rows of any length and nothing passes through
 // hash_tmp.  Their trees are k_merkle_level<M> / k_merkle_subtree<M> of kernels.hpp on k3::Merge and rp::Merge (and, for the
-// top of the Rp64_256 tree, k_rp64_merkle_subtree of rescue_kernels.hpp).
+// top of the Rp64_256 tree, k_merkle_subtree_lanes of rescue_kernels.hpp).
 #pragma once
 #include "kernels.hpp"
 

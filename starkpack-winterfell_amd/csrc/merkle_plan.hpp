@@ -21,12 +21,12 @@ struct MerklePlan {
 constexpr MerklePlan MERKLE_PLAN_BLAKE3 = {true, 15, 16, 9, 256, 256};
 // Sha3_256: the one-lane-per-node rule of BLAKE3 without a two-level kernel.
 constexpr MerklePlan MERKLE_PLAN_SHA3 = {false, 15, 0, 9, 256, 256};
-// Rp64_256: the sub-tree kernel is the lane form (16 lanes per parent, rp::permute_lane).  The switch is measured
+// Rp64_256: the sub-tree kernel is the lane form (k_merkle_subtree_lanes<rp::Lanes>: 16 lanes per parent, rp::permute_lane).  The switch is measured
 // (docs/EXPERIMENTS.md "Rp64_256", scripts/rescue_bench.hip): a level of up to 2^16 parents costs one permutation's latency
 // with one lane per parent (0.33 ms), the lane form's latency is a ninth of that and its throughput 73 %, so it wins up to
 // 2^15 parents.
 constexpr MerklePlan MERKLE_PLAN_RP64 = {false, 16, 0, 7, 64, 1024};
-// RpJive64_256: the sub-tree kernel is the lane form with 8 lanes per parent and none idle (rpj::merge_lane), so a
+// RpJive64_256: the sub-tree kernel is the same lane form (<rpj::Lanes>) with 8 lanes per parent and none idle (rpj::merge_lane), so a
 // work-group of 1024 lanes spans 128 parents and folds 8 levels.  The switch is measured (docs/EXPERIMENTS.md
 // "RpJive64_256", scripts/rescue_jive_bench.hip, profiles/rpjive_rescue_bench.txt).  One level, ms, lane per parent / lane
 // form: 2^13 0.219 / 0.068, 2^14 0.219 / 0.071, 2^15 0.224 / 0.075, 2^16 0.230 / 0.131, 2^17 0.297 / 0.238, 2^18 0.507 / 0.443,

@@ -8,8 +8,7 @@
 #include "keccak_kernels.hpp"
 #include "merkle_plan.hpp"
 #include "rescue_kernels.hpp"
-#include "rescue_jive_kernels.hpp"
-#include "griffin_dev.hpp"
+#include "hasher_dispatch.hpp"
 #include "seg_kernels.hpp"
 #include "col_kernels.hpp"
 #include "fri_kernels.hpp"
@@ -702,20 +701,16 @@ static int run_hash_rows(wf_ctx *ctx, hipStream_t st, const void *lde, uint64_t 
     const uint32_t threads = 256;
     const uint64_t grid = (n_rows + threads - 1) / threads;
     if (hasher != WF_HASH_BLAKE3) {  // the sponge hashers: one lane per row absorbs the whole row, whatever its length
-        if (hasher == WF_HASH_RP64_256 && F::FIELD_ID != 1) return fail(WF_ERR_FIELD, "Rp64_256 hashes elements of the f64 field only");
-        if (hasher == WF_HASH_RPJIVE64_256 && F::FIELD_ID != 1) return fail(WF_ERR_FIELD, "RpJive64_256 hashes elements of the f64 field only");
-        if (hasher == WF_HASH_GRIFFINJIVE64_256 && F::FIELD_ID != 1) return fail(WF_ERR_FIELD, "GriffinJive64_256 hashes elements of the f64 field only");
+        int rc = check_hasher_field(hasher, F::FIELD_ID);
+        if (rc) return rc;
         if (grid > 0x7FFFFFFFull) return fail(WF_ERR_ARG, "too many rows for one launch");
-        if (hasher == WF_HASH_SHA3_256)
-            hipLaunchKernelGGL((k_hash_rows_sponge<F, k3::Absorb>), dim3((uint32_t)grid), dim3(threads), 0, st, h);
-        else if constexpr (F::FIELD_ID == 1) {  // (the sponge takes the stored (Montgomery) elements as they are)
-            if (hasher == WF_HASH_RPJIVE64_256)
-                hipLaunchKernelGGL((k_hash_rows_sponge<F, rpj::Absorb>), dim3((uint32_t)grid), dim3(threads), 0, st, h);
-            else if (hasher == WF_HASH_GRIFFINJIVE64_256)
-                hipLaunchKernelGGL((k_hash_rows_sponge<F, gfj::Absorb>), dim3((uint32_t)grid), dim3(threads), 0, st, h);
-            else
-                hipLaunchKernelGGL((k_hash_rows_sponge<F, rp::Absorb>), dim3((uint32_t)grid), dim3(threads), 0, st, h);
-        }
+        dispatch_hasher(hasher, digest_bytes, [&](auto tag) {
+            typedef decltype(tag) T;
+            // (an element-digest sponge takes the stored (Montgomery) elements as they are: instantiated for f64 only)
+            if constexpr (!std::is_void<typename T::Absorb>::value && (!T::F64_ONLY || F::FIELD_ID == 1))
+                hipLaunchKernelGGL((k_hash_rows_sponge<F, typename T::Absorb>), dim3((uint32_t)grid), dim3(threads), 0, st, h);
+            return 0;
+        });
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -753,11 +748,15 @@ static int run_hash_rows(wf_ctx *ctx, hipStream_t st, const void *lde, uint64_t 
 }
 
 // The tree of every hasher: the launches merkle_next_launch (merkle_plan.hpp) names for the hasher's plan, each level
-// written to nodes[n .. 2n).  M: the hasher's merge policy (only a plan with two-level launches instantiates
-// k_merkle_level2<M>).  A pure kernel sequence.
+// written to nodes[n .. 2n).  T: the hasher's tag (hasher_dispatch.hpp) -- its merge policy M (only a plan with two-level
+// launches instantiates k_merkle_level2<M>) and, where the sub-tree kernel is the lane form, its lane policy L.  A pure
+// kernel sequence.
 // (nodes[0] = Digest::default(), merkle/mod.rs:355, is written by the launch that produces the root)
-template <class M, const MerklePlan &PLAN>
+template <class T>
 static int run_merkle_plan(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes) {
+    typedef typename T::Merge M;
+    typedef typename T::Lanes L;
+    constexpr const MerklePlan &PLAN = T::PLAN;
     typedef typename M::W W;
     const W *children = (const W *)leaves;
     W *const out = (W *)nodes;
@@ -771,12 +770,10 @@ static int run_merkle_plan(wf_ctx *ctx, hipStream_t st, const void *leaves, uint
         if (s.kind == MERKLE_LEVEL) {
             hipLaunchKernelGGL(k_merkle_level<M>, grid, block, 0, st, children, out + n_par * M::NW, n_par);
         } else if (s.kind == MERKLE_SUBTREE) {
-            if constexpr (std::is_same<M, rp::Merge>::value)
-                hipLaunchKernelGGL(k_rp64_merkle_subtree, grid, block, 0, st, children, out, n_children, s.levels);
-            else if constexpr (std::is_same<M, rpj::Merge>::value)
-                hipLaunchKernelGGL(k_rpjive_merkle_subtree, grid, block, 0, st, children, out, n_children, s.levels);
-            else
+            if constexpr (std::is_void<L>::value)
                 hipLaunchKernelGGL(k_merkle_subtree<M>, grid, block, 0, st, children, out, n_children, s.levels);
+            else
+                hipLaunchKernelGGL(k_merkle_subtree_lanes<L>, grid, block, 0, st, children, out, n_children, s.levels);
         } else if constexpr (PLAN.two_level) {  // MERKLE_LEVEL2
             hipLaunchKernelGGL(k_merkle_level2<M>, grid, block, 0, st, children, out + n_par * M::NW, out + s.n_children * M::NW,
                                s.n_children);
@@ -790,12 +787,8 @@ static int run_merkle_plan(wf_ctx *ctx, hipStream_t st, const void *leaves, uint
 
 static int run_merkle(wf_ctx *ctx, hipStream_t st, const void *leaves, uint64_t n_leaves, void *nodes, uint32_t hasher,
                       uint32_t digest_bytes) {
-    if (hasher == WF_HASH_SHA3_256) return run_merkle_plan<k3::Merge, MERKLE_PLAN_SHA3>(ctx, st, leaves, n_leaves, nodes);
-    if (hasher == WF_HASH_RP64_256) return run_merkle_plan<rp::Merge, MERKLE_PLAN_RP64>(ctx, st, leaves, n_leaves, nodes);
-    if (hasher == WF_HASH_RPJIVE64_256) return run_merkle_plan<rpj::Merge, MERKLE_PLAN_RPJIVE>(ctx, st, leaves, n_leaves, nodes);
-    if (hasher == WF_HASH_GRIFFINJIVE64_256) return run_merkle_plan<gfj::Merge, MERKLE_PLAN_GRIFFIN>(ctx, st, leaves, n_leaves, nodes);
-    return digest_bytes == 24 ? run_merkle_plan<b3::Merge<6>, MERKLE_PLAN_BLAKE3>(ctx, st, leaves, n_leaves, nodes)
-                              : run_merkle_plan<b3::Merge<8>, MERKLE_PLAN_BLAKE3>(ctx, st, leaves, n_leaves, nodes);
+    return dispatch_hasher(hasher, digest_bytes,
+                           [&](auto tag) { return run_merkle_plan<decltype(tag)>(ctx, st, leaves, n_leaves, nodes); });
 }
 
 // ------------------------------------------------------------------------------------------------- the path (device)

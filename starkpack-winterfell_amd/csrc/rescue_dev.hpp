@@ -25,6 +25,7 @@
 // tests/test_rescue_host.py pins them to tests/golden/rp64_256_params.json, scripts/gen_rp64_fixtures.py --header prints them.
 #pragma once
 #include "field.hpp"
+#include "merkle_plan.hpp"
 
 namespace wf {
 namespace rp {
@@ -326,6 +327,7 @@ struct Merge {
     static constexpr int NW = DIGEST;
     static constexpr bool HAS_QUAD = false;
     static WF_HD void merge(const W (&in)[2 * NW], W (&out)[NW]) { rp::merge(in, out); }
+    static WF_HD void merge_with_int_mont(const W (&seed)[NW], uint64_t value, W (&out)[NW]) { rp::merge_with_int_mont(seed, value, out); }
 };
 struct Absorb {
     static constexpr bool CANONICAL = false;
@@ -337,6 +339,19 @@ struct Absorb {
 WF_HD uint64_t merge_lane_init(uint32_t i, uint64_t w) {
     return i == 0 ? elem_new(RATE) : (i >= (uint32_t)RATE_AT && i < (uint32_t)STATE) ? elem_new(w) : 0;
 }
+
+#if defined(__HIPCC__)
+// The hasher as k_merkle_subtree_lanes (rescue_kernels.hpp) takes it: groups of 16 lanes, lane e holds state element e.
+// Lanes 4..11 load / carry one digest word each, lane 0 the element count, lanes 12..15 nothing; lanes 4..7 end with the
+// parent's digest word e - 4.  merge_lane runs inside the kernel's wave-uniform branch (every lane of the wave active),
+// digest_word behind it.
+struct Lanes {
+    static constexpr const MerklePlan &PLAN = MERKLE_PLAN_RP64;
+    static constexpr uint32_t LOG_LANES = 4, WORD_AT = RATE_AT, DIGEST_AT = RATE_AT;
+    static __device__ __forceinline__ uint64_t merge_lane(uint32_t e, uint64_t w) { return permute_lane(merge_lane_init(e, w)); }
+    static __device__ __forceinline__ uint64_t digest_word(uint64_t x) { return F64::to_canonical(x); }
+};
+#endif
 
 }  // namespace rp
 }  // namespace wf

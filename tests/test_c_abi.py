@@ -1,6 +1,7 @@
 """include/wf_lde.h is plain C: tests/c/test_abi.c is compiled with gcc -std=c99 -Wall -Wextra -Werror -pedantic and
 run -- without a GPU it exercises the host-side entry points and checks that context creation fails loudly (exit 77);
 on the GPU box it runs a commitment, a resident commitment and queries through the ABI as a C host would."""
+import ctypes
 import os
 import subprocess
 import tempfile
@@ -25,6 +26,33 @@ def test_header_is_c99_and_host_side_runs_without_a_gpu(capi):
     out = build_and_run(capi)
     assert out.returncode == 77, out.stdout + out.stderr
     assert "compute skipped" in out.stdout
+
+
+def test_params_check_on_every_hasher_id(capi):
+    """wf_params_check over hasher ids 0..32: which ids exist, which digest sizes and fields each of them takes."""
+    lib = capi.load()
+    known = {0: b"BLAKE3", 1: b"Sha3_256", 16: b"Rp64_256", 18: b"RpJive64_256", 20: b"GriffinJive64_256"}
+    f64_only = {16, 18, 20}
+    WF_ERR_FIELD, WF_ERR_DIGEST = -10, -31
+
+    def check(hasher, field=capi.F64, digest_bytes=32):
+        return lib.wf_params_check(ctypes.byref(capi.make_params(field, 1, 10, 3, 8, 1, digest_bytes=digest_bytes, hasher=hasher)), 0)
+
+    for hasher in range(33):
+        if hasher not in known:
+            assert check(hasher) == WF_ERR_DIGEST, hasher
+            msg = lib.wf_last_error()
+            for i, name in known.items():
+                assert b"%d = %s" % (i, name) in msg, (hasher, msg)
+            assert check(hasher, digest_bytes=24) == WF_ERR_DIGEST, hasher
+            continue
+        assert check(hasher) == 0, hasher
+        assert check(hasher, digest_bytes=24) == (0 if hasher == 0 else WF_ERR_DIGEST), hasher
+        if hasher != 0:
+            assert known[hasher] in lib.wf_last_error()
+        assert check(hasher, field=capi.F128) == (WF_ERR_FIELD if hasher in f64_only else 0), hasher
+        if hasher in f64_only:
+            assert known[hasher] in lib.wf_last_error()
 
 
 @pytest.mark.gpu

@@ -145,7 +145,7 @@ def _directed_pairs(h):
 
 
 def test_merkle_subtree_on_directed_pairs(hs):
-    """2^7 leaves, every pair a directed one: the bottom level runs in k_rp64_merkle_subtree / k_rpjive_merkle_subtree, the
+    """2^7 leaves, every pair a directed one: the bottom level runs in k_merkle_subtree_lanes<rp::Lanes> / <rpj::Lanes>, the
     lane form of the linear layer (lane_mds_ark).  Against the C reference and the Python one."""
     h, c = hs
     leaves = _directed_pairs(h)

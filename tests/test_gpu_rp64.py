@@ -15,7 +15,7 @@ from loopback import Loopback
 pytestmark = pytest.mark.gpu
 F64, F128 = 1, 2
 P = R.P
-SPAN = 64         # parents per work-group of k_rp64_merkle_subtree (RP64_SUBTREE_SPAN, csrc/rescue_kernels.hpp)
+SPAN = 64         # parents per work-group of k_merkle_subtree_lanes<rp::Lanes> (MERKLE_PLAN_RP64.subtree_span, csrc/merkle_plan.hpp)
 BUDGET = 2048     # reference permutations per test
 
 
@@ -120,8 +120,8 @@ def test_combined_rows_of_several_traces(capi, ctx, orc, n_traces, n_cols):
 #   a level of >= 2^16 parents (>= 2^17 children) is one k_merkle_level<rp::Merge> launch (one lane per parent): 2^15 and 2^16
 #   leaves below the switch, 2^17 at it (the switch is a measured one and came out one level above where a 2^16-leaf tree
 #   would still cross it);
-#   below that k_rp64_merkle_subtree (16 lanes per parent, 64 parents per work-group) folds up to 7 levels per launch:
-#   2^1 .. 2^6 leaves a partly filled work-group, 2^7 exactly seven levels in one launch, 2^8 seven levels + a second launch
+#   below that k_merkle_subtree_lanes<rp::Lanes> (16 lanes per parent, 64 parents per work-group) folds up to 7 levels per launch:
+#   2^1 .. 2^6 leaves a partly filled work-group (2^4 and 2^5: 8 and 16 of its 64 groups), 2^7 exactly seven levels in one launch, 2^8 seven levels + a second launch
 #   of one, 2^9 and 2^10 several work-groups in the first launch.
 def _leaves(log_n):
     n = 1 << log_n
@@ -147,7 +147,7 @@ def _build_dev(rctx, leaves):
     return d_nodes.cpu().numpy()
 
 
-@pytest.mark.parametrize("log_n", [1, 2, 3, 6, 7, 8, 9, 10])
+@pytest.mark.parametrize("log_n", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10])
 def test_merkle_build_in_full(rctx, log_n):
     leaves = _leaves(log_n)
     want = R.merkle_nodes(leaves)

@@ -17,7 +17,7 @@ from loopback import Loopback
 pytestmark = pytest.mark.gpu
 F64, F128 = 1, 2
 P = R.P
-SPAN = 128        # parents per work-group of k_rpjive_merkle_subtree (RPJIVE_SUBTREE_SPAN, csrc/rescue_jive_kernels.hpp)
+SPAN = 128        # parents per work-group of k_merkle_subtree_lanes<rpj::Lanes> (MERKLE_PLAN_RPJIVE.subtree_span, csrc/merkle_plan.hpp)
 BUDGET = 2048     # reference permutations per test
 
 
@@ -142,7 +142,7 @@ def test_combined_rows_of_several_traces(capi, ctx, orc, n_traces, n_cols):
 # The switches of the tree (MERKLE_PLAN_RPJIVE, csrc/merkle_plan.hpp):
 #   a level of >= 2^17 parents (>= 2^18 children) is one k_merkle_level<rpj::Merge> launch (one lane per parent): 2^16 and
 #   2^17 leaves below the switch, 2^18 at it;
-#   below that k_rpjive_merkle_subtree (8 lanes per parent, 128 parents per work-group of 16 waves) folds up to 8 levels per
+#   below that k_merkle_subtree_lanes<rpj::Lanes> (8 lanes per parent, 128 parents per work-group of 16 waves) folds up to 8 levels per
 #   launch: 2^1 .. 2^3 leaves one to four groups of one wave, 2^4 exactly one wave, 2^5 two waves, 2^6 and 2^7 a partly idle
 #   work-group, 2^8 exactly eight levels in one launch, 2^9 two work-groups and a second launch of one level, 2^10 four.
 def _leaves(log_n):
