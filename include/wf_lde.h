@@ -415,8 +415,8 @@ int wf_constraint_commit_from_tables(wf_ctx *ctx, const wf_params *p, const wf_e
  *   out_regs[j] may be of either type (a base value is embedded when stored).  Every result is the field value, i.e. what the
  *   reference computes; the reference evaluates main transition constraints in the base field and merges them with
  *   coef.mul_base (evaluator.rs:266-275) -- a program that keeps that order keeps its products cheap.
- * Refused, before anything is launched: WF_ERR_ARG for null pointers, non-zero reserved fields, an unknown op or source (source
- *   kinds from 7 on are reserved for the auxiliary frame), counts outside the ranges below, a dst / register / constant / table /
+ * Refused, before anything is launched: WF_ERR_ARG for null pointers, non-zero reserved fields, an unknown op or source (7 and 8
+ *   are the auxiliary frame, accepted by wf_constraint_evaluate_aux only; kinds from 9 on are reserved), counts outside the ranges below, a dst / register / constant / table /
  *   column index out of range, a register read before it is written or written with a second type, an out_regs entry never
  *   written, a constant or table value that is not a valid field element, shift >= 2^log2_len or 2^log2_len > ce,
  *   trace_index >= n_traces, registers that take more than 64 (f64) / 32 (f128) base elements (a base register counts once, an
@@ -457,6 +457,33 @@ typedef struct wf_cprog {
 typedef struct wf_evaluations wf_evaluations;
 int wf_constraint_evaluate(const wf_commitment *trace, uint32_t trace_index, const wf_cprog *prog, uint32_t ext_degree,
                            uint32_t log2_ce_blowup, wf_evaluations **out);
+/* ---- constraint programs over the main AND the auxiliary segment (RAP AIRs) ------------------------------------------------
+ * evaluate_fragment_full of the reference (prover/src/constraints/evaluator.rs:190-241): the program reads a second frame from
+ * the auxiliary segment's LDE (TraceLde::read_aux_trace_frame_into, prover/src/trace/trace_lde.rs:100-108) and is the whole of
+ * that branch -- main transition constraints in the base field merged with mul_base, auxiliary transition constraints in E,
+ * boundary constraints of both segments; the random elements arrive as ECONST.  One auxiliary segment, as in the reference.
+ *
+ * Everything wf_constraint_evaluate documents holds with main_trace / main_index in the role of trace / trace_index: row mapping,
+ * X, CONST / ECONST / TABLE, typing, output layout, ordering and lifetime (both commitments' kernels are ahead of the call on
+ * the context's stream; handles of wf_trace_commit_resident_async are valid input for either).  In addition
+ *   AUX_CUR c  = element c of E of LDE row lde_step of matrix aux_index of aux_trace,
+ *   AUX_NEXT c = the same element of row (lde_step + lde_blowup) mod n,
+ *   where an element of E in a row is the ext_degree consecutive base elements at c * ext_degree, as wf_commitment_read_lde
+ *   returns that commitment's rows; c < n_cols of the auxiliary commitment.  Both sources are of type E (with ext_degree == 1 the
+ *   types coincide, as for ECONST).
+ * The result is an ordinary wf_evaluations handle.  A program without auxiliary sources is accepted and produces the bytes of
+ * wf_constraint_evaluate.
+ * Refused, before anything is launched and with *out untouched: every refusal of wf_constraint_evaluate with its code (a main
+ *   commitment of ext_degree != 1, WF_ERR_EXTENSION and WF_ERR_BLOWUP included), and WF_ERR_ARG for a null main_trace,
+ *   aux_trace, prog or out; an aux_trace of another context; an auxiliary field, log2_trace_len, log2_blowup or domain_offset
+ *   that differs from the main commitment's; aux_trace->p.ext_degree != ext_degree; an auxiliary commitment that holds no rows;
+ *   aux_index >= n_traces of the auxiliary commitment; an auxiliary column index >= n_cols of the auxiliary commitment; a
+ *   source kind >= 9; a frame that does not fit -- the budget is the one above, 320 f64 / 160 f128 base elements for main frame
+ *   columns, auxiliary frame columns at ext_degree each, x and registers together. */
+enum { WF_CP_AUX_CUR = 7, WF_CP_AUX_NEXT = 8 }; /* accepted by wf_constraint_evaluate_aux only */
+int wf_constraint_evaluate_aux(const wf_commitment *main_trace, uint32_t main_index, const wf_commitment *aux_trace,
+                               uint32_t aux_index, const wf_cprog *prog, uint32_t ext_degree, uint32_t log2_ce_blowup,
+                               wf_evaluations **out);
 int wf_evaluations_info(const wf_evaluations *e, uint32_t *n_columns, uint64_t *ce_domain_size, uint32_t *ext_degree);
 /* column `column` as ce_domain_size elements of E into host memory; waits for the evaluation */
 int wf_evaluations_read(const wf_evaluations *e, uint32_t column, void *out);

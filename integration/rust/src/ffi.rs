@@ -64,6 +64,57 @@ pub struct WfQuery {
     pub depth: u32,
 }
 
+/// `wf_cprog_instr`: dst = a op b (ops 1 ADD, 2 SUB, 3 MUL; sources `WF_CP_*`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct WfCprogInstr {
+    pub op: u8,
+    pub a_src: u8,
+    pub b_src: u8,
+    pub reserved0: u8,
+    pub dst: u16,
+    pub a: u16,
+    pub b: u16,
+    pub reserved1: u16,
+}
+/// `wf_cprog_table`: the value at `step` is values[(step - shift) mod 2^log2_len].
+#[repr(C)]
+pub struct WfCprogTable {
+    pub values: *const c_void,
+    pub log2_len: u32,
+    pub reserved: u32,
+    pub shift: u64,
+}
+/// `wf_cprog`: a straight-line constraint program.
+#[repr(C)]
+pub struct WfCprog {
+    pub instrs: *const WfCprogInstr,
+    pub n_instrs: u32,
+    pub n_regs: u32,
+    pub consts: *const c_void,
+    pub n_consts: u32,
+    pub econsts: *const c_void,
+    pub n_econsts: u32,
+    pub tables: *const WfCprogTable,
+    pub n_tables: u32,
+    pub out_regs: *const u16,
+    pub n_out: u32,
+}
+pub const WF_CP_REG: u8 = 0;
+pub const WF_CP_CUR: u8 = 1;
+pub const WF_CP_NEXT: u8 = 2;
+pub const WF_CP_CONST: u8 = 3;
+pub const WF_CP_ECONST: u8 = 4;
+pub const WF_CP_TABLE: u8 = 5;
+pub const WF_CP_X: u8 = 6;
+/// the auxiliary segment's frame: accepted by `wf_constraint_evaluate_aux` only
+pub const WF_CP_AUX_CUR: u8 = 7;
+pub const WF_CP_AUX_NEXT: u8 = 8;
+#[repr(C)]
+pub struct WfEvaluations {
+    _private: [u8; 0],
+}
+
 #[repr(C)]
 pub struct WfFriProver {
     _private: [u8; 0],
@@ -122,6 +173,20 @@ extern "C" {
         ctx: *mut WfCtx, p: *const WfParams, tables: *const WfEvaluationTable, n_tables: usize, ce_domain_size: usize,
         final_coeff: *const c_void, polys_out: *const *mut c_void, out: *mut *mut WfCommitment,
     ) -> c_int;
+    // constraint programs on the resident trace LDE
+    pub fn wf_constraint_evaluate(
+        trace: *const WfCommitment, trace_index: u32, prog: *const WfCprog, ext_degree: u32, log2_ce_blowup: u32,
+        out: *mut *mut WfEvaluations,
+    ) -> c_int;
+    pub fn wf_constraint_evaluate_aux(
+        main_trace: *const WfCommitment, main_index: u32, aux_trace: *const WfCommitment, aux_index: u32,
+        prog: *const WfCprog, ext_degree: u32, log2_ce_blowup: u32, out: *mut *mut WfEvaluations,
+    ) -> c_int;
+    pub fn wf_evaluations_info(
+        e: *const WfEvaluations, n_columns: *mut u32, ce_domain_size: *mut u64, ext_degree: *mut u32,
+    ) -> c_int;
+    pub fn wf_evaluations_read(e: *const WfEvaluations, column: u32, out: *mut c_void) -> c_int;
+    pub fn wf_evaluations_destroy(e: *mut WfEvaluations);
     pub fn wf_deep_compose(
         ctx: *mut WfCtx, trace_commitments: *const *const WfCommitment, n_trace_commitments: usize,
         constraint_commitment: *const WfCommitment, z: *const c_void, ext_degree: u32, trace_coeffs: *const c_void,

@@ -26,8 +26,10 @@
 //! f128 as canonical `u128`, extension elements as consecutive base elements (`extensions/quadratic.rs:26-28`).
 //!
 //! The constraint evaluation between the two commitments (`prover/src/lib.rs:386-410`) has a resident form too:
-//! `wf_constraint_evaluate` runs a constraint program (`wf_cprog`, include/wf_lde.h) on the resident trace LDE.  This crate
-//! does not bind it yet and has no tracer: the program is what `Air::evaluate_transition` does to a frame, so running that
+//! `wf_constraint_evaluate` runs a constraint program (`wf_cprog`, include/wf_lde.h) on the resident trace LDE, and
+//! `wf_constraint_evaluate_aux` one that also reads the auxiliary segment's frame (`WF_CP_AUX_CUR` / `WF_CP_AUX_NEXT`: RAP
+//! AIRs, `evaluate_fragment_full`).  This crate binds both (`constraint_evaluate`, `constraint_evaluate_aux`) as thin wrappers
+//! over a caller-built `WfCprog` and has no tracer: the program is what `Air::evaluate_transition` does to a frame, so running that
 //! method once on an element type that records additions, subtractions and products (with `frame.current()[c]` /
 //! `frame.next()[c]` as the CUR / NEXT sources and the periodic values as TABLE sources) yields it; the boundary constraints
 //! add `(cur[c] - value) * coefficient` columns.
@@ -495,6 +497,72 @@ where
         check(rc).expect("failed to read the extended trace");
         (rows, width as usize)
     }
+}
+
+/// The evaluation columns of a constraint program, left in device memory (`wf_evaluations`).
+pub struct ResidentEvaluations<'a> {
+    raw: *mut WfEvaluations,
+    _ctx: PhantomData<&'a WfContext>,
+}
+
+impl<'a> ResidentEvaluations<'a> {
+    pub fn as_ptr(&self) -> *const WfEvaluations {
+        self.raw
+    }
+
+    /// Column `column` as ce_domain_size elements of E (waits for the evaluation).
+    pub fn read<E: FieldElement>(&self, column: usize) -> Vec<E> {
+        let (mut n_columns, mut ce, mut ext) = (0u32, 0u64, 0u32);
+        check(unsafe { wf_evaluations_info(self.raw, &mut n_columns, &mut ce, &mut ext) }).expect("info");
+        assert_eq!(ext as usize, E::EXTENSION_DEGREE);
+        let mut out: Vec<E> = unsafe { uninit_vector(ce as usize) };
+        check(unsafe { wf_evaluations_read(self.raw, column as u32, out.as_mut_ptr() as *mut c_void) }).expect("read");
+        out
+    }
+}
+
+impl<'a> Drop for ResidentEvaluations<'a> {
+    fn drop(&mut self) {
+        unsafe { wf_evaluations_destroy(self.raw) }
+    }
+}
+
+/// `wf_constraint_evaluate`: the program on the resident LDE of matrix `trace_index` of a main-segment commitment.
+/// `prog` and everything it points to only has to live until the call returns.
+pub fn constraint_evaluate<'a, B, E, H>(
+    trace: &ResidentCommitment<'a, B, H>, trace_index: usize, prog: &WfCprog, log2_ce_blowup: u32,
+) -> Result<ResidentEvaluations<'a>, String>
+where
+    B: WfField,
+    E: FieldElement<BaseField = B>,
+    H: WfHasher,
+{
+    let mut raw = core::ptr::null_mut();
+    check(unsafe {
+        wf_constraint_evaluate(trace.raw, trace_index as u32, prog, E::EXTENSION_DEGREE as u32, log2_ce_blowup, &mut raw)
+    })?;
+    Ok(ResidentEvaluations { raw, _ctx: PhantomData })
+}
+
+/// `wf_constraint_evaluate_aux`: `evaluate_fragment_full` (prover/src/constraints/evaluator.rs:190-241) -- the program also
+/// reads `WF_CP_AUX_CUR` / `WF_CP_AUX_NEXT`, elements of E of the frame of matrix `aux_index` of the auxiliary segment's
+/// commitment (committed with `ext_degree` = `E::EXTENSION_DEGREE`).
+pub fn constraint_evaluate_aux<'a, B, E, H>(
+    main: &ResidentCommitment<'a, B, H>, main_index: usize, aux: &ResidentCommitment<'a, E, H>, aux_index: usize, prog: &WfCprog,
+    log2_ce_blowup: u32,
+) -> Result<ResidentEvaluations<'a>, String>
+where
+    B: WfField,
+    E: FieldElement<BaseField = B>,
+    H: WfHasher,
+{
+    let mut raw = core::ptr::null_mut();
+    check(unsafe {
+        wf_constraint_evaluate_aux(
+            main.raw, main_index as u32, aux.raw, aux_index as u32, prog, E::EXTENSION_DEGREE as u32, log2_ce_blowup, &mut raw,
+        )
+    })?;
+    Ok(ResidentEvaluations { raw, _ctx: PhantomData })
 }
 
 /// `DeepCompositionPoly::new(z, cc)` + `add_trace_polys` + `add_composition_poly` + `evaluate(&domain)` +

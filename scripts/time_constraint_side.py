@@ -11,7 +11,10 @@ The device-evaluated route next to the host-table one, interleaved round by roun
        bound of the route a host had before.
   cfg 2: f64, 2^20 x 8, blowup 8 (programs fib -- memory-bound -- and stress -- ALU-bound); cfg 5: f128, 2^18 x 10, the do_work
   program.  ce blowup 4, quadratic extension.  Also prints the planner's work-group size and LDS bytes, the kernel's device time,
-  the bytes it moves and the base-field products it executes per second."""
+  the bytes it moves and the base-field products it executes per second.
+
+The same comparison for an AIR with an auxiliary segment (wf_constraint_evaluate_aux; old: the read-back of BOTH LDEs):
+    python scripts/time_constraint_side.py aux [rounds]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -100,6 +103,78 @@ def device_route(cfg, rounds, name):
     ctx.close()
 
 
+def aux_route(rounds):
+    """cfg 2's shape with an auxiliary segment: f64, 2^20 x 8 main columns, 4 auxiliary columns of the quadratic extension, ce
+    blowup 4, the permutation argument on all four auxiliary columns (tests/cprog_aux_util.py: perm, n = 4)."""
+    import ctypes as C
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import cprog_aux_util as A
+    import cprog_util as U
+    import edge_util as E
+    field, logR, n_cols, n_aux, ext, logB, lce, n_cols_c = capi.F64, 20, 8, 4, 2, 3, 2, 2
+    R, ce = 1 << logR, 1 << (logR + lce)
+    ctx = capi.Context(0)
+    rng = np.random.default_rng(2)
+    com, _ = ctx.trace_commit_resident(capi.make_params(field, 1, logR, logB, n_cols, 1),
+                                       [rng.integers(0, 2**62, size=R, dtype=np.uint64) for _ in range(n_cols)])
+    aux, _ = ctx.trace_commit_resident(capi.make_params(field, ext, logR, logB, n_aux, 1),
+                                       [rng.integers(0, 2**62, size=R * ext, dtype=np.uint64) for _ in range(n_aux)])
+    g = A.perm(field, ext, [U.draw_e(rng, field, ext) for _ in range(n_aux)], n_aux)
+    prog = U.to_capi(capi, g, field, ext)
+    one = E.elements(field, [E.ONE[field]])
+    gR = E.elements(field, [U.to_mem(field, pow(U.root_of_unity(field, logR), R - 1, U.P[field]))])
+    divs = [(R, one, gR)] * n_aux + [(1, one, None)] * n_aux
+    p = capi.make_params(field, ext, logR, logB, n_cols_c, 1)
+    ev = ctx.constraint_evaluate_aux(com, 0, aux, 0, prog, ext, lce)
+    host_cols = [ev.read(j) for j in range(ev.n_columns)]
+    ev.close()
+    L = capi.load()
+    rw, arw = C.c_uint64(), C.c_uint64()
+    L.wf_commitment_read_lde(com._h, 0, 0, 0, None, C.byref(rw))
+    L.wf_commitment_read_lde(aux._h, 0, 0, 0, None, C.byref(arw))
+    bufs = [np.zeros((ce, w.value), dtype=np.uint64) for w in (rw, arw)]   # touched: no page faults in the clock
+    stride = 1 << (logB - lce)
+    new_ms, old_ms, read_ms = [], [], []
+    roots = set()
+    for r in range(rounds + 1):
+        t0 = time.perf_counter()
+        ev = ctx.constraint_evaluate_aux(com, 0, aux, 0, prog, ext, lce)
+        c_new, _ = ctx.constraint_commit_from_device_tables(p, [(ev, divs)])
+        t1 = time.perf_counter()
+        for h, buf, w in ((com, bufs[0], rw), (aux, bufs[1], arw)):
+            capi._check(L.wf_commitment_read_lde_strided(h._h, 0, 0, ce, stride, buf.ctypes.data_as(C.c_void_p), C.byref(w)))
+        t2 = time.perf_counter()
+        c_old, _ = ctx.constraint_commit_from_tables(p, [list(zip(host_cols, divs))])
+        t3 = time.perf_counter()
+        roots |= {c_new.root(), c_old.root()}
+        ev.close(); c_new.close(); c_old.close()
+        if r:  # round 0 warms tables and the buffer pool up
+            new_ms.append((t1 - t0) * 1e3); old_ms.append((t3 - t1) * 1e3); read_ms.append((t2 - t1) * 1e3)
+            print(f"round {r}: new {new_ms[-1]:8.2f} ms | old {old_ms[-1]:8.2f} ms (read_lde_strided of both {read_ms[-1]:.2f} + from_tables {old_ms[-1] - read_ms[-1]:.2f})", flush=True)
+    assert len(roots) == 1, "the two routes disagree"
+    med = lambda v: sorted(v)[len(v) // 2]
+    print(f"aux perm x{n_aux}: median new {med(new_ms):.2f} ms, old (lower bound) {med(old_ms):.2f} ms of which the read-back {med(read_ms):.2f} ms "
+          f"({sum(b.nbytes for b in bufs) >> 20} MiB); ratio {med(old_ms) / med(new_ms):.2f}x; {len(host_cols)} columns of {host_cols[0].nbytes >> 20} MiB")
+    ctx.profile_enable(2)
+    for _ in range(5):
+        ctx.constraint_evaluate_aux(com, 0, aux, 0, prog, ext, lce).close()
+    ks = sorted(v for k, v in ctx.profile_read() if k == "constraint.evaluate_aux")
+    k_ms = ks[len(ks) // 2]
+    types, cur, nxt, acur, anxt = A.typing(g, ext)
+    used = (len(cur) + len(nxt) + (len(acur) + len(anxt)) * ext) * 8 * ce
+    written = len(g.out_regs) * ext * 8 * ce
+    # whole rows, per matrix the rows the program reads at all: step << shift and / or their successors (distinct: stride >= 2)
+    rows = ce * 8 * (rw.value * (bool(cur) + bool(nxt)) + arw.value * (bool(acur) + bool(anxt)))
+    print(f"kernel {ks[0]:.3f} / {k_ms:.3f} / {ks[-1]:.3f} ms (min / median / max of {len(ks)}): {len(g.instrs)} instructions; frame elements used "
+          f"{used >> 20} MiB + columns written {written >> 20} MiB = {(used + written) / k_ms / 1e9:.3f} TB/s; whole rows touched {rows >> 20} MiB, "
+          f"{(rows + written) / k_ms / 1e9:.3f} TB/s")
+    com.close(); aux.close()
+    ctx.close()
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "aux":
+    aux_route(int(sys.argv[2]) if len(sys.argv) > 2 else 5)
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "device":
     device_route(int(sys.argv[2]), int(sys.argv[3]) if len(sys.argv) > 3 else 5, sys.argv[4] if len(sys.argv) > 4 else None)
     sys.exit(0)

@@ -35,7 +35,7 @@ SYMBOLS = [
     "wf_comm_max_f64", "wf_comm_gather_f64", "wf_comm_info", "wf_shard_proofs", "wf_shard_cosets", "wf_shard_route", "wf_comm_all_gather_leaf_shards",
     "wf_trace_commit_sharded_dev", "wf_trace_commit_sharded_resident", "wf_sharded_commitment_destroy",
     "wf_sharded_commitment_root", "wf_sharded_commitment_query", "wf_sharded_commitment_polys",
-    "wf_constraint_evaluate", "wf_evaluations_info", "wf_evaluations_read", "wf_evaluations_destroy",
+    "wf_constraint_evaluate", "wf_constraint_evaluate_aux", "wf_evaluations_info", "wf_evaluations_read", "wf_evaluations_destroy",
     "wf_constraint_commit_from_device_tables",
 ]
 
@@ -76,6 +76,7 @@ class EvaluationTable(C.Structure):
 # enum wf_cprog_op / wf_cprog_src (constraint programs)
 CP_ADD, CP_SUB, CP_MUL = 1, 2, 3
 CP_REG, CP_CUR, CP_NEXT, CP_CONST, CP_ECONST, CP_TABLE, CP_X = 0, 1, 2, 3, 4, 5, 6
+CP_AUX_CUR, CP_AUX_NEXT = 7, 8  # the auxiliary segment's frame: Context.constraint_evaluate_aux only
 
 
 class CprogInstr(C.Structure):
@@ -287,6 +288,7 @@ def load():
         L.wf_sharded_commitment_query.argtypes = [vp, vp, sz, vp, vp, vp, sz, vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(u32)]
         L.wf_sharded_commitment_polys.argtypes = [vp, C.POINTER(vp)]
         L.wf_constraint_evaluate.argtypes = [vp, u32, C.POINTER(Cprog), u32, u32, C.POINTER(vp)]
+        L.wf_constraint_evaluate_aux.argtypes = [vp, u32, vp, u32, C.POINTER(Cprog), u32, u32, C.POINTER(vp)]
         L.wf_evaluations_info.argtypes = [vp, pu32, pu64, pu32]
         L.wf_evaluations_read.argtypes = [vp, u32, vp]
         L.wf_evaluations_destroy.argtypes = [vp]
@@ -564,6 +566,17 @@ class Context:
         h = C.c_void_p()
         _check(load().wf_constraint_evaluate(trace._h, trace_index, C.byref(prog), ext_degree, log2_ce_blowup, C.byref(h)))
         return Evaluations(h, trace.field, keep_alive=self)
+
+    def constraint_evaluate_aux(self, main: "Commitment", main_index: int, aux: "Commitment", aux_index: int, prog, ext_degree: int,
+                                log2_ce_blowup: int) -> "Evaluations":
+        """wf_constraint_evaluate_aux: constraint_evaluate for an AIR with an auxiliary segment (a RAP) -- the program also reads
+        CP_AUX_CUR / CP_AUX_NEXT, elements of E of the frame of matrix `aux_index` of the commitment `aux` (ext_degree columns)."""
+        if isinstance(prog, tuple):
+            prog = prog[0]
+        h = C.c_void_p()
+        _check(load().wf_constraint_evaluate_aux(main._h, main_index, aux._h, aux_index, C.byref(prog), ext_degree, log2_ce_blowup,
+                                                 C.byref(h)))
+        return Evaluations(h, main.field, keep_alive=self)
 
     def constraint_commit_from_device_tables(self, params: Params, tables, final_coeff=None, want_polys=False):
         """wf_constraint_commit_from_device_tables: tables = [(Evaluations, [(a, b, exemptions) per column])] per packed trace

@@ -1,5 +1,6 @@
 // libwf_lde.so, unit 8 of 8 -- constraint programs: ConstraintEvaluator::evaluate (prover/src/constraints/evaluator.rs:74-241)
-// for the main trace segment on the resident trace LDE.  The host side plans the caller's program (cprog_plan.hpp), uploads
+// on the resident trace LDE: the main segment alone (wf_constraint_evaluate) or the main and the auxiliary segment
+// (wf_constraint_evaluate_aux: evaluate_fragment_full, :190-241).  The host side plans the caller's program (cprog_plan.hpp), uploads
 // its kernel form in one piece and launches the interpreter (cprog_kernels.hpp); the evaluation columns stay in device memory
 // (wf_evaluations) for wf_constraint_commit_from_device_tables (path.hip).
 #include "wf_internal.hpp"
@@ -25,15 +26,17 @@ static void free_evaluations(wf_evaluations *e) {
 static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 template <class F, int WE>
-static int evaluate_dev(wf_ctx *ctx, hipStream_t st, const wf_commitment *c, uint32_t trace_index, const wf_cprog *prog,
-                        const CpPlan &pl, wf_evaluations *e) {
+static int evaluate_dev(wf_ctx *ctx, hipStream_t st, const wf_commitment *c, uint32_t trace_index, const wf_commitment *aux,
+                        uint32_t aux_index, const wf_cprog *prog, const CpPlan &pl, wf_evaluations *e) {
     typedef typename F::T T;
     const size_t eb = sizeof(T);
     // the program as the kernel reads it, one upload: instructions | frame | outputs | table descriptors | constants | tables
+    // | aux frame (last: a program without auxiliary sources is uploaded as it always was)
     const size_t o_instr = 0, o_frame = align16(o_instr + pl.instrs.size() * sizeof(CpInstr));
     const size_t o_outs = align16(o_frame + pl.frame.size() * 4), o_tdesc = align16(o_outs + pl.out_slot.size() * 4);
     const size_t o_const = align16(o_tdesc + pl.tables.size() * sizeof(CpTable)), o_tval = align16(o_const + pl.n_const_elems * eb);
-    const size_t total = align16(o_tval + pl.n_table_elems * eb);
+    const size_t o_aux = align16(o_tval + pl.n_table_elems * eb);
+    const size_t total = align16(o_aux + pl.aux_frame.size() * 4);
     HIP_TRY(hipHostMalloc(&e->prog_host, total, hipHostMallocDefault));
     unsigned char *h = (unsigned char *)e->prog_host;
     memset(h, 0, total);
@@ -43,6 +46,7 @@ static int evaluate_dev(wf_ctx *ctx, hipStream_t st, const wf_commitment *c, uin
         const uint32_t o = pl.out_slot[j] | (pl.out_is_ext[j] ? 1u << 31 : 0u);
         memcpy(h + o_outs + j * 4, &o, 4);
     }
+    if (!pl.aux_frame.empty()) memcpy(h + o_aux, pl.aux_frame.data(), pl.aux_frame.size() * 4);
     if (!pl.tables.empty()) memcpy(h + o_tdesc, pl.tables.data(), pl.tables.size() * sizeof(CpTable));
     {
         size_t off = o_const;
@@ -92,32 +96,50 @@ static int evaluate_dev(wf_ctx *ctx, hipStream_t st, const wf_commitment *c, uin
     memcpy(&off, c->p.domain_offset, 16);
     a.offset = F::from_u128_canonical(off);
     a.g = as_pow2l<F>(*tw);
-    if (pl.lds_bytes > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)k_cprog_eval<F, WE>, hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS_BYTES));
-    prof_mark(ctx, st, "constraint.evaluate");
-    hipLaunchKernelGGL((k_cprog_eval<F, WE>), dim3((uint32_t)((pl.ce + pl.group_size - 1) / pl.group_size)), dim3(pl.group_size),
-                       pl.lds_bytes, st, a);
+    const dim3 grid((uint32_t)((pl.ce + pl.group_size - 1) / pl.group_size)), block(pl.group_size);
+    if (pl.aux_frame.empty()) {  // nothing is read from the auxiliary segment: the main kernel
+        if (pl.lds_bytes > 64 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void *)k_cprog_eval<F, WE>, hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS_BYTES));
+        prof_mark(ctx, st, "constraint.evaluate");
+        hipLaunchKernelGGL((k_cprog_eval<F, WE>), grid, block, pl.lds_bytes, st, a);
+    } else {
+        CprogAuxArgs<F> x;
+        memset(&x, 0, sizeof(x));
+        x.lde = (const T *)aux->lde + (size_t)aux_index * aux->n_rows * aux->row_width;
+        x.frame = (const uint32_t *)(d + o_aux);
+        x.n_frame = (uint32_t)pl.aux_frame.size();
+        x.base = pl.aux_base;
+        x.row_width = (uint32_t)aux->row_width;
+        if (pl.lds_bytes > 64 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void *)k_cprog_eval_aux<F, WE>, hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS_BYTES));
+        prof_mark(ctx, st, "constraint.evaluate_aux");
+        hipLaunchKernelGGL((k_cprog_eval_aux<F, WE>), grid, block, pl.lds_bytes, st, a, x);
+    }
     HIP_TRY(hipGetLastError());
     prof_mark(ctx, st, "between_calls");
     return 0;
 }
 
-extern "C" {
-
-int wf_constraint_evaluate(const wf_commitment *trace, uint32_t trace_index, const wf_cprog *prog, uint32_t ext_degree,
-                           uint32_t log2_ce_blowup, wf_evaluations **out) {
-    if (!trace) return fail(WF_ERR_ARG, "commitment is null");
-    if (!out) return fail(WF_ERR_ARG, "out is null");
+static CpShape shape_of(const wf_commitment *c) {
     CpShape sh;
-    sh.field = trace->p.field;
-    sh.trace_ext = trace->p.ext_degree;
-    sh.n_cols = trace->p.n_cols;
-    sh.n_traces = trace->p.n_traces;
-    sh.log2_trace_len = trace->p.log2_trace_len;
-    sh.log2_blowup = trace->p.log2_blowup;
-    sh.has_lde = trace->lde != nullptr && trace->row_width >= trace->p.n_cols;
+    sh.field = c->p.field;
+    sh.trace_ext = c->p.ext_degree;
+    sh.n_cols = c->p.n_cols;
+    sh.n_traces = c->p.n_traces;
+    sh.log2_trace_len = c->p.log2_trace_len;
+    sh.log2_blowup = c->p.log2_blowup;
+    sh.has_lde = c->lde != nullptr && c->row_width >= (uint64_t)c->p.n_cols * c->p.ext_degree;
+    return sh;
+}
+
+// both entry points; aux == nullptr: the main segment only
+static int evaluate(const wf_commitment *trace, uint32_t trace_index, const wf_commitment *aux, uint32_t aux_index, const wf_cprog *prog,
+                    uint32_t ext_degree, uint32_t log2_ce_blowup, wf_evaluations **out) {
+    const CpShape sh = shape_of(trace);
+    CpShape sh_aux;
+    if (aux) sh_aux = shape_of(aux);
     CpPlan pl;
-    int rc = cprog_plan(prog, sh, trace_index, ext_degree, log2_ce_blowup, pl);
+    int rc = cprog_plan_aux(prog, sh, aux ? &sh_aux : nullptr, trace_index, aux_index, ext_degree, log2_ce_blowup, pl);
     if (rc) return fail(rc, "%s", pl.msg);
     wf_ctx *ctx = trace->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -132,12 +154,12 @@ int wf_constraint_evaluate(const wf_commitment *trace, uint32_t trace_index, con
     e->n_columns = prog->n_out;
     e->ce = pl.ce;
     if (sh.field == WF_FIELD_F64)
-        rc = ext_degree == 1   ? evaluate_dev<F64, 1>(ctx, st, trace, trace_index, prog, pl, e)
-             : ext_degree == 2 ? evaluate_dev<F64, 2>(ctx, st, trace, trace_index, prog, pl, e)
-                               : evaluate_dev<F64, 3>(ctx, st, trace, trace_index, prog, pl, e);
+        rc = ext_degree == 1   ? evaluate_dev<F64, 1>(ctx, st, trace, trace_index, aux, aux_index, prog, pl, e)
+             : ext_degree == 2 ? evaluate_dev<F64, 2>(ctx, st, trace, trace_index, aux, aux_index, prog, pl, e)
+                               : evaluate_dev<F64, 3>(ctx, st, trace, trace_index, aux, aux_index, prog, pl, e);
     else
-        rc = ext_degree == 1 ? evaluate_dev<F128, 1>(ctx, st, trace, trace_index, prog, pl, e)
-                             : evaluate_dev<F128, 2>(ctx, st, trace, trace_index, prog, pl, e);
+        rc = ext_degree == 1 ? evaluate_dev<F128, 1>(ctx, st, trace, trace_index, aux, aux_index, prog, pl, e)
+                             : evaluate_dev<F128, 2>(ctx, st, trace, trace_index, aux, aux_index, prog, pl, e);
     if (rc) {
         (void)hipStreamSynchronize(st);  // whatever was queued into the handle's buffers has drained before they go away
         free_evaluations(e);
@@ -145,6 +167,27 @@ int wf_constraint_evaluate(const wf_commitment *trace, uint32_t trace_index, con
     }
     *out = e;
     return 0;
+}
+
+extern "C" {
+
+int wf_constraint_evaluate(const wf_commitment *trace, uint32_t trace_index, const wf_cprog *prog, uint32_t ext_degree,
+                           uint32_t log2_ce_blowup, wf_evaluations **out) {
+    if (!trace) return fail(WF_ERR_ARG, "commitment is null");
+    if (!out) return fail(WF_ERR_ARG, "out is null");
+    return evaluate(trace, trace_index, nullptr, 0, prog, ext_degree, log2_ce_blowup, out);
+}
+
+int wf_constraint_evaluate_aux(const wf_commitment *main_trace, uint32_t main_index, const wf_commitment *aux_trace, uint32_t aux_index,
+                               const wf_cprog *prog, uint32_t ext_degree, uint32_t log2_ce_blowup, wf_evaluations **out) {
+    if (!main_trace) return fail(WF_ERR_ARG, "main commitment is null");
+    if (!aux_trace) return fail(WF_ERR_ARG, "auxiliary commitment is null");
+    if (!out) return fail(WF_ERR_ARG, "out is null");
+    if (aux_trace->ctx != main_trace->ctx || aux_trace->ctx_generation != main_trace->ctx_generation)
+        return fail(WF_ERR_ARG, "the auxiliary commitment belongs to another context");
+    if (memcmp(aux_trace->p.domain_offset, main_trace->p.domain_offset, sizeof(main_trace->p.domain_offset)))
+        return fail(WF_ERR_ARG, "the auxiliary commitment's domain_offset differs from the main commitment's");
+    return evaluate(main_trace, main_index, aux_trace, aux_index, prog, ext_degree, log2_ce_blowup, out);
 }
 
 int wf_evaluations_info(const wf_evaluations *e, uint32_t *n_columns, uint64_t *ce_domain_size, uint32_t *ext_degree) {

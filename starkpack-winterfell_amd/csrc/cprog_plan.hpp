@@ -7,11 +7,15 @@
 //   - refuses whatever the header lists as refused (cprog_plan returns the status, CpPlan::msg says why),
 //   - infers the type of every register (base field or E; fixed by the first write),
 //   - collects the frame columns the program reads (the kernel loads only those),
-//   - lays the lane's state out in LDS slots of one base element: [frame columns][x][registers], an E register WE slots,
+//   - lays the lane's state out in LDS slots of one base element: [frame columns][aux frame columns][x][registers], an E
+//     register and an aux frame column WE slots,
 //   - rewrites the program into the kernel's form: the op split by operand types (BB / EB / BE / EE), REG / CUR / NEXT / X
 //     resolved to slots, CONST / ECONST to offsets into one constant buffer that holds only what is referenced, TABLE to an
 //     entry of the table descriptors (again only the referenced ones),
 //   - chooses the work-group size from the LDS footprint.
+// cprog_plan_aux is the planner of wf_constraint_evaluate_aux: with the shape of an auxiliary commitment it accepts the sources
+// AUX_CUR / AUX_NEXT (elements of E of the auxiliary segment's frame, trace_lde.rs:100-108); cprog_plan is the same function
+// without one, where those kinds stay unknown sources.
 #pragma once
 #include <stdarg.h>
 #include <stdint.h>
@@ -66,6 +70,8 @@ struct CpPlan {
     std::vector<uint8_t> reg_type;         // per caller register: 0 never written, 1 base, 2 E
     std::vector<uint32_t> reg_slot;        // first slot of a written register
     std::vector<uint32_t> frame;           // column | (NEXT ? 1 << 16 : 0), ascending; entry i lives in slot i
+    std::vector<uint32_t> aux_frame;       // the same of the auxiliary segment (columns of E); entry i lives in slots aux_base + i * ext ..
+    uint32_t aux_base = 0;
     uint32_t x_slot = CP_NO_SLOT;
     uint32_t reg_base = 0, reg_footprint = 0, n_slots = 0;
     std::vector<uint32_t> const_src;       // the constant buffer: index | (ECONST ? 1 << 31 : 0), an ECONST takes ext elements
@@ -111,8 +117,9 @@ inline uint32_t cp_group_size(uint32_t bytes_per_lane) {
     return 64;
 }
 
-inline int cprog_plan(const wf_cprog *prog, const CpShape &sh, uint32_t trace_index, uint32_t ext_degree, uint32_t log2_ce_blowup,
-                      CpPlan &pl) {
+// sh_aux == nullptr: main segment only (wf_constraint_evaluate)
+inline int cprog_plan_aux(const wf_cprog *prog, const CpShape &sh, const CpShape *sh_aux, uint32_t trace_index, uint32_t aux_index,
+                          uint32_t ext_degree, uint32_t log2_ce_blowup, CpPlan &pl) {
     pl.msg[0] = 0;
     if (!prog) return cp_fail(pl, WF_ERR_ARG, "prog is null");
     if (sh.field != WF_FIELD_F64 && sh.field != WF_FIELD_F128) return cp_fail(pl, WF_ERR_FIELD, "unknown field id %u", sh.field);
@@ -125,6 +132,16 @@ inline int cprog_plan(const wf_cprog *prog, const CpShape &sh, uint32_t trace_in
         return cp_fail(pl, WF_ERR_EXTENSION, "unsupported extension degree %u for field %u", ext_degree, sh.field);
     if (log2_ce_blowup == 0 || log2_ce_blowup > sh.log2_blowup)
         return cp_fail(pl, WF_ERR_BLOWUP, "constraint evaluation blowup 2^%u is not in [2, 2^%u]", log2_ce_blowup, sh.log2_blowup);
+    if (sh_aux) {
+        if (sh_aux->field != sh.field || sh_aux->log2_trace_len != sh.log2_trace_len || sh_aux->log2_blowup != sh.log2_blowup)
+            return cp_fail(pl, WF_ERR_ARG, "the auxiliary commitment (field %u, 2^%u rows, blowup 2^%u) is not of the main commitment's shape (field %u, 2^%u rows, blowup 2^%u)",
+                           sh_aux->field, sh_aux->log2_trace_len, sh_aux->log2_blowup, sh.field, sh.log2_trace_len, sh.log2_blowup);
+        if (sh_aux->trace_ext != ext_degree)
+            return cp_fail(pl, WF_ERR_ARG, "the auxiliary commitment holds columns of extension degree %u, the program runs in degree %u",
+                           sh_aux->trace_ext, ext_degree);
+        if (!sh_aux->has_lde) return cp_fail(pl, WF_ERR_ARG, "the auxiliary commitment holds no rows");
+        if (aux_index >= sh_aux->n_traces) return cp_fail(pl, WF_ERR_ARG, "auxiliary trace %u of %u", aux_index, sh_aux->n_traces);
+    }
     const uint32_t eb = sh.field == WF_FIELD_F64 ? 8 : 16, WE = ext_degree;
     const uint64_t ce = (uint64_t)1 << (sh.log2_trace_len + log2_ce_blowup);
     pl.field = sh.field;
@@ -164,6 +181,8 @@ inline int cprog_plan(const wf_cprog *prog, const CpShape &sh, uint32_t trace_in
     const uint32_t NI = prog->n_instrs;
     pl.reg_type.assign(prog->n_regs, 0);
     std::vector<uint8_t> cur_used(sh.n_cols, 0), next_used(sh.n_cols, 0);
+    const uint32_t n_aux_cols = sh_aux ? sh_aux->n_cols : 0;
+    std::vector<uint8_t> aux_cur_used(n_aux_cols, 0), aux_next_used(n_aux_cols, 0);
     std::vector<uint8_t> typing(NI);
     bool x_used = false;
     for (uint32_t i = 0; i < NI; i++) {
@@ -198,6 +217,13 @@ inline int cprog_plan(const wf_cprog *prog, const CpShape &sh, uint32_t trace_in
                 case WF_CP_X:
                     x_used = true;
                     break;
+                case WF_CP_AUX_CUR:
+                case WF_CP_AUX_NEXT:
+                    if (!sh_aux) return cp_fail(pl, WF_ERR_ARG, "instruction %u: unknown operand source %u", i, src);
+                    if (idx >= n_aux_cols) return cp_fail(pl, WF_ERR_ARG, "instruction %u: auxiliary column %u of %u", i, idx, n_aux_cols);
+                    (src == WF_CP_AUX_CUR ? aux_cur_used : aux_next_used)[idx] = 1;
+                    if (WE > 1) ty[o] = 2;
+                    break;
                 default:
                     return cp_fail(pl, WF_ERR_ARG, "instruction %u: unknown operand source %u", i, src);
             }
@@ -222,7 +248,7 @@ inline int cprog_plan(const wf_cprog *prog, const CpShape &sh, uint32_t trace_in
     if (pl.reg_footprint > max_fp)
         return cp_fail(pl, WF_ERR_ARG, "the registers take %u base elements (at most %u)", pl.reg_footprint, max_fp);
 
-    // ---- slots: [frame columns][x][registers in register order]
+    // ---- slots: [frame columns][aux frame columns, WE slots each][x][registers in register order]
     std::vector<uint32_t> cur_slot(sh.n_cols, CP_NO_SLOT), next_slot(sh.n_cols, CP_NO_SLOT);
     pl.frame.clear();
     for (uint32_t c = 0; c < sh.n_cols; c++)
@@ -236,6 +262,20 @@ inline int cprog_plan(const wf_cprog *prog, const CpShape &sh, uint32_t trace_in
             pl.frame.push_back(c | (1u << 16));
         }
     uint32_t slot = (uint32_t)pl.frame.size();
+    std::vector<uint32_t> aux_cur_slot(n_aux_cols, CP_NO_SLOT), aux_next_slot(n_aux_cols, CP_NO_SLOT);
+    pl.aux_frame.clear();
+    pl.aux_base = slot;
+    for (uint32_t c = 0; c < n_aux_cols; c++)
+        if (aux_cur_used[c]) {
+            aux_cur_slot[c] = pl.aux_base + (uint32_t)pl.aux_frame.size() * WE;
+            pl.aux_frame.push_back(c);
+        }
+    for (uint32_t c = 0; c < n_aux_cols; c++)
+        if (aux_next_used[c]) {
+            aux_next_slot[c] = pl.aux_base + (uint32_t)pl.aux_frame.size() * WE;
+            pl.aux_frame.push_back(c | (1u << 16));
+        }
+    slot += (uint32_t)pl.aux_frame.size() * WE;
     pl.x_slot = x_used ? slot++ : CP_NO_SLOT;
     pl.reg_base = slot;
     pl.reg_slot.assign(prog->n_regs, CP_NO_SLOT);
@@ -246,6 +286,9 @@ inline int cprog_plan(const wf_cprog *prog, const CpShape &sh, uint32_t trace_in
         }
     pl.n_slots = slot;
     pl.group_size = cp_group_size(pl.n_slots * eb);
+    if (!pl.group_size && !pl.aux_frame.empty())
+        return cp_fail(pl, WF_ERR_ARG, "%u frame columns, %u auxiliary frame columns of degree %u and %u register elements of %u bytes do not fit the local memory of a compute unit",
+                       (uint32_t)pl.frame.size(), (uint32_t)pl.aux_frame.size(), WE, pl.reg_footprint, eb);
     if (!pl.group_size)
         return cp_fail(pl, WF_ERR_ARG, "%u frame columns and %u register elements of %u bytes do not fit the local memory of a compute unit",
                        (uint32_t)pl.frame.size(), pl.reg_footprint, eb);
@@ -274,6 +317,8 @@ inline int cprog_plan(const wf_cprog *prog, const CpShape &sh, uint32_t trace_in
                 case WF_CP_CUR: v = cur_slot[idx]; break;
                 case WF_CP_NEXT: v = next_slot[idx]; break;
                 case WF_CP_X: v = pl.x_slot; break;
+                case WF_CP_AUX_CUR: v = aux_cur_slot[idx]; break;
+                case WF_CP_AUX_NEXT: v = aux_next_slot[idx]; break;
                 case WF_CP_CONST:
                     kind = CPK_CONST;
                     if (const_off[idx] == CP_NO_SLOT) {
@@ -316,6 +361,11 @@ inline int cprog_plan(const wf_cprog *prog, const CpShape &sh, uint32_t trace_in
         pl.out_is_ext[j] = pl.reg_type[prog->out_regs[j]] == 2;
     }
     return 0;
+}
+
+inline int cprog_plan(const wf_cprog *prog, const CpShape &sh, uint32_t trace_index, uint32_t ext_degree, uint32_t log2_ce_blowup,
+                      CpPlan &pl) {
+    return cprog_plan_aux(prog, sh, nullptr, trace_index, 0, ext_degree, log2_ce_blowup, pl);
 }
 
 }  // namespace wf
